@@ -8,7 +8,12 @@ A "step" = one decode step of the whole batch (c new tokens) through the C++ run
 (hipGraph replay); `value` = output tokens/s summed over all GPUs.  Per SURVEY.md §8(e) the reference does
 not shard this MoE config, so N GPUs run N independent replicas ("scaling": "weak").
 
-Tensor parallel (the dense BASELINE configs): with N > 1 ranks the same launch ALSO times
+A plain run sets up, warms up, times the `--steps` steps and prints the line.  `--full` also measures everything else: the
+whole 128-step workload window (`e2e_tok_s`, `vs_baseline`), per-kernel and roofline figures, the c sweep and TTFT, the
+closed-loop serve driver, the CPU baseline and the tensor-parallel extras below.  `--dump-outputs DIR` writes the sampled
+token ids of the last timed step to DIR (inputs are seeded: two builds can be compared output for output).
+
+Tensor parallel (the dense BASELINE configs): with N > 1 ranks a `--full` launch ALSO times
 Llama-3 70B GPTQ-INT4 (configs[4]) as ONE tensor-parallel group of N ranks — per-rank shards (heads, kv heads
 and intermediate ÷ N), RCCL all-reduce after o_proj and down_proj captured inside the per-rank decode hipGraph —
 and reports it under `tp_scaling` (N = 2 adds Gemma-3 27B, configs[3]); N = 1 reports the same models unsharded,
@@ -289,11 +294,13 @@ def _dist_dev(dist):
     return "cuda" if dist.get_backend() == "nccl" else "cpu"
 
 
-def tp_decode_case(pkg, torch, dist, model_name, world, rank, c, PL, steps, warm, chunk, try_oneshot=True, transport="rccl", layers=None):
+def tp_decode_case(pkg, torch, dist, model_name, world, rank, c, PL, steps, warm, chunk, try_oneshot=True, transport="rccl", layers=None,
+                   last_tokens=None):
     """One tensor-parallel group of `world` ranks (this process = rank `rank`) decoding `c` sequences of a dense model:
     per-rank shards, a communicator per rank (RCCL shared through a broadcast unique id; or, transport "oneshot", only the
     hand-written peer reduce over hipIpc buffers), prefill, `warm` + `steps` decode steps through the per-rank hipGraph
-    (all-reduces captured).  Returns the whole-group rate (the slowest rank's time)."""
+    (all-reduces captured).  Returns the whole-group rate (the slowest rank's time); `last_tokens` (a list), when given,
+    receives the ids the last timed step sampled."""
     cfg = shard_cfg(MODELS[model_name], world, rank)
     max_seq_len = ((PL + 2 * (warm + steps) + 8 + 15) // 16) * 16
     t0 = time.perf_counter()
@@ -347,6 +354,8 @@ def tp_decode_case(pkg, torch, dist, model_name, world, rank, c, PL, steps, warm
         return float(t[0].item()), float(t[1].item()), out
 
     t_dec, t_pre, out = run(0)
+    if last_tokens is not None:
+        last_tokens.append(out[-1].copy())
     res = {"model": model_name, "tp": world, "concurrency": c, "steps": steps, "warmup": warm, "tok_s": round(c * steps / t_dec, 1),
            "ms_per_step": round(t_dec / steps * 1e3, 4), "prefill_ms": round(t_pre * 1e3, 2), "build_s": round(build_s, 1),
            "allreduce": ("none (TP=1)" if world == 1 else
@@ -396,6 +405,14 @@ def tp_decode_case(pkg, torch, dist, model_name, world, rank, c, PL, steps, warm
     return res
 
 
+def dump_outputs(dirname, rank, tokens):
+    """--dump-outputs: what the timed path hands its caller in its last step — the sampled id of every sequence — as float64
+    (ids are exact).  One file per rank: replicas decode prompts of their own."""
+    os.makedirs(dirname, exist_ok=True)
+    name = "decode_tokens" if rank == 0 else f"decode_tokens_rank{rank}"
+    np.save(os.path.join(dirname, name + ".npy"), np.asarray(tokens, np.float64))
+
+
 def main():
     ap = argparse.ArgumentParser()
     ap.add_argument("--gpus", type=int, default=1)
@@ -416,7 +433,14 @@ def main():
     ap.add_argument("--no-tp-scaling", action="store_true", help="skip the dense tensor-parallel extra (tp_scaling)")
     ap.add_argument("--no-sweep", action="store_true")
     ap.add_argument("--no-cpu-baseline", action="store_true")
+    ap.add_argument("--full", action="store_true", help="also measure what the headline does not need: the whole 128-step window, "
+                    "per-kernel / roofline / north-star kernel figures, the c sweep and TTFT, the serve loop, the CPU baseline and the "
+                    "tensor-parallel extras (the --no-* options above trim this set)")
+    ap.add_argument("--dump-outputs", metavar="DIR", help="after the timed steps, write the ids the last timed step sampled to "
+                    "DIR/decode_tokens.npy (float64, one per sequence; rank r > 0: decode_tokens_rank<r>.npy)")
     args = ap.parse_args()
+    if args.steps < 1 or args.warmup < 0:
+        ap.error("--steps must be >= 1 and --warmup >= 0")
 
     import torch
     rank = int(os.environ.get("RANK", "0"))
@@ -466,11 +490,11 @@ def main():
         nxt = warm_toks[-1] if warm > 0 else first
         barrier()
         t0 = time.perf_counter()
-        model.decode_steps(ids, nxt, steps)
+        toks = model.decode_steps(ids, nxt, steps)
         torch.cuda.synchronize()
         t_local = time.perf_counter() - t0
         barrier()
-        return t_local, PL + warm + steps
+        return t_local, PL + warm + steps, toks[-1]
 
     _last_stage = ["start"]
 
@@ -482,8 +506,11 @@ def main():
 
     if args.tp:
         # a dense BASELINE config as ONE tensor-parallel group: the headline line of this invocation
+        last = []
         res = tp_decode_case(pkg, torch, dist, args.model, world, rank, c, PL, K, W, min(chunk, 2048), try_oneshot=args.tp_oneshot,
-                             transport=args.tp_transport, layers=args.layers or None)
+                             transport=args.tp_transport, layers=args.layers or None, last_tokens=last)
+        if args.dump_outputs:
+            dump_outputs(args.dump_outputs, rank, last[0])
         if rank == 0:
             mname = {"llama31-8b": "Llama-3.1-8B", "gemma3-27b": "Gemma-3-27B", "llama3-70b": "Llama-3-70B"}[args.model]
             print(json.dumps({
@@ -500,8 +527,10 @@ def main():
 
     model = build_model(pkg, cfg, c, max_seq_len, chunk, 9271 + rank, layers=args.layers or None)
     stage("model built")
-    t_local, kv_end = run_case(model, c, K, W, 0)
+    t_local, kv_end, last = run_case(model, c, K, W, 0)
     stage("timed decode done")
+    if args.dump_outputs:
+        dump_outputs(args.dump_outputs, rank, last)
     t = torch.tensor([t_local], dtype=torch.float64, device="cuda")
     if dist is not None:
         dist.all_reduce(t, op=dist.ReduceOp.MAX)
@@ -512,10 +541,10 @@ def main():
     # the BASELINE workload's whole decode window, whatever --steps says: 128 steps from kv 256 to 384 on fresh sequences
     # (no warm-up steps inside the window; the graph is already captured for this batch size or re-captured at the bucket edge)
     full = None
-    if not args.tp and c * (PL + OUT_LEN) <= 10 ** 7:
+    if args.full and not args.tp and c * (PL + OUT_LEN) <= 10 ** 7:
         for sid in range(c):
             model.release(sid)
-        t_full, _ = run_case(model, c, OUT_LEN, 0, 50000)
+        t_full, _, _ = run_case(model, c, OUT_LEN, 0, 50000)
         tf = torch.tensor([t_full, prefill_ms[c] / 1e3], dtype=torch.float64, device="cuda")
         if dist is not None:
             dist.all_reduce(tf, op=dist.ReduceOp.MAX)
@@ -527,7 +556,7 @@ def main():
         for sid in range(50000, 50000 + c):
             model.release(sid)
         stage("full 128-step window done")
-    if rank == 0:
+    if rank == 0 and args.full:
         # dominant kernel: MoE gate_up grouped INT4 GEMM — live HIP-event timing on the runner's stream
         kernels = {}
         mlp_names = ("moe_gate_up", "moe_down") if moe else ("gate_up", "down")
@@ -619,7 +648,7 @@ def main():
             sweep = {str(c): round(value, 1)}
             ttft = []
             for conc in (1, 4, 16):
-                tl, _ = run_case(model, conc, min(K, 32), 4, 1000 * conc)
+                tl, _, _ = run_case(model, conc, min(K, 32), 4, 1000 * conc)
                 sweep[str(conc)] = round(conc * min(K, 32) / tl, 1)
                 for s in range(1000 * conc, 1000 * conc + conc):
                     model.release(s)
@@ -715,7 +744,7 @@ def main():
     # They run AFTER everything the headline needs has been measured, under a watchdog: a multi-GPU collective that never
     # completes (these paths have not run on a multi-GPU node yet) must cost the extras, not the line — past the deadline rank 0
     # prints the line without them and every rank leaves.
-    if not args.no_tp_scaling and not args.layers and args.model == "qwen3-30b-a3b" and world in (1, 2, 4, 8):
+    if args.full and not args.no_tp_scaling and not args.layers and args.model == "qwen3-30b-a3b" and world in (1, 2, 4, 8):
         import threading
 
         def bail_out():
