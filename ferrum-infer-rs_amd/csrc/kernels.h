@@ -70,18 +70,10 @@ struct MoeRouteLists {
     int T = 0, Q = 0, norm_topk = 0;
     int32_t* pub_expert_ids = nullptr; float* pub_expert_w = nullptr;
 };
-bool w4_gemm_moe_expert_major_pair_supports(const W4Device& gu, const W4Device& dn, int num_experts, int num_valid_pairs,
-                                            const MoeRouteLists* route);
+bool w4_gemm_moe_expert_major_pair_supports(const W4Device& gu, const W4Device& dn, int num_experts, int num_valid_pairs);
 int w4_gemm_moe_expert_major_pair(const W4Device& gu, const W4Device& dn, const __half* x, __half* h, __half* out,
                                   const int32_t* pair_expert_ids, int num_experts, int num_valid_pairs, int top_k,
-                                  unsigned* arrive, unsigned* arrive_next, unsigned* timeout, int* took, hipStream_t stream,
-                                  const MoeRouteLists* route = nullptr);
-bool w4_gemm_moe_block_major_pair_supports(const W4Device& gu, const W4Device& dn, int num_experts, int num_valid_pairs, int max_blocks,
-                                           const MoeRouteLists* route);
-int w4_gemm_moe_block_major_pair(const W4Device& gu, const W4Device& dn, const __half* x, __half* h, __half* out,
-                                 const int32_t* pair_expert_ids, int num_experts, int num_valid_pairs, int max_blocks, int top_k,
-                                 unsigned* arrive, unsigned* arrive_next, unsigned* timeout, int* took, hipStream_t stream,
-                                 const MoeRouteLists* route = nullptr);
+                                  unsigned* arrive, unsigned* arrive_next, unsigned* timeout, int* took, hipStream_t stream);
 int w4_gemm_moe_inline_align(const W4Device& w, const __half* x, __half* out, const int32_t* pair_expert_ids,
                              int num_experts, int num_valid_pairs, int max_blocks, int top_k, int fused_silu,
                              int32_t* pub_sorted, int32_t* pub_block_ids, int32_t* pub_total, hipStream_t stream,

@@ -40,16 +40,13 @@ struct Knobs {
     int chain_max_keys = 4096;        // decode chain only up to this many keys per attention workgroup (× T·nkv / 128)
     int dense_chain = 1;              // dense models at 17–32 rows: the attention half of the layer as the chain launch too (0 = five launches)
     int moe_em2 = 1;                  // decode: gate_up → down as one expert-major launch (0 = two launches)
-    int moe_bm2 = 0;                  // decode at ≤ 64 pairs: gate_up → down as one block-major launch — measured slower than the two launches (profiles/r03_moe_bm2_timeline.txt): off
     int moe_deferred_merge = 1;       // decode chain: the grouped GEMM's prologue merges the router's candidate lists (0 = role B does)
     int w4_tile_min_m = 0;
     int w4_tile_wgs = 256;
     int w4_ldsa = 1;
     int w4_ldsa_nw = 0;
     int w4_ldsa_s = 0;
-    int w4_ldsw = 0;             // EXPERIMENTS builds: 17–32-row dense GEMM through w4_gemm_ldsw_kernel (3 or 6 = ring slots)
     int w4_big = 0;                   // 0 auto, −1 never, 8 / 16 forces w4_gemm_big_kernel's 128- / 256-row tiles
-    int w4_ldsk = 0;                  // EXPERIMENTS=1 builds only: nw·100 + kw·10 + d forces a w4_gemm_ldsk_kernel form (+1000: ares)
     int w4_nt = 0;
     int w4_w = 0;
     int lds_min_wgs = 128;
@@ -100,7 +97,6 @@ enum Form : int {
     FORM_W4_FUSED_TAIL,         // ≤ 4-row q|k|v GEMM with the previous layer's combine + add + norm as its prologue
     FORM_ATTN_RESIDENT,         // short-prompt prefill: the sequence's K/V resident in LDS
     FORM_W4_BIG,                // prefill: 128- / 256-row tiles, scale folded into the fp16 B operand
-    FORM_W4_LDSK,               // 17–64 rows: LDS-shared activations, K split over the waves of a workgroup
     FORM_GATHER_COLUMNS,        // act-order input gather as a launch of its own (no producer wrote the permuted row)
     FORM_PERM_PRODUCER,         // act-order: the producing kernel (norm, gated activation via gate_up's column order, decode attention) wrote the permuted row
     FORM_MOE_EXPERT_MAJOR_PAIR, // gate_up → down in one expert-major launch (in-launch hand-off per expert)
@@ -108,7 +104,6 @@ enum Form : int {
     FORM_MOE_DEFERRED_MERGE,    // the merged grouped GEMM took the routing as per-part candidate lists and merged them itself
     FORM_DENSE_CHAIN,           // dense model: tail + q|k|v + attention + o_proj + add/norm as the one chain launch (chain.hip)
     FORM_TP_ALLREDUCE_NORM_FUSED, // tensor parallel: one-shot all-reduce + residual add + norm as one launch
-    FORM_MOE_BLOCK_MAJOR_PAIR,  // ≤ 64 pairs: gate_up → down in one block-major launch (in-launch hand-off per 16-row block)
     FORM_CHAIN_ATTN_KV_SPLITS,  // decode chain with several KV ranges per (sequence, kv head) in its attention role (ticket merge)
     FORM_CHAIN_QKV_WIDE,        // decode chain with 128-column q|k|v blocks (the narrow ones + attention exceed the resident workgroups)
     FORM_ROUTE_GEMM_TOPK,       // prefill router: logits (MFMA) + softmax + top-k in one launch (moe_route_gemm_topk_kernel)

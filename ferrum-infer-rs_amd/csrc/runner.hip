@@ -1079,20 +1079,13 @@ static bool moe_pair_form(const FerrumHipModel* m, const LayerWeights& L, int P)
            m->em2_arrive && !m->em2_failed && !L.exp_down.perm;
 }
 static bool moe_deferred_merge_ok(const FerrumHipModel* m, const LayerWeights& L, int T, int Q) {
-    const int mode = knobs().moe_deferred_merge;
-    if (!mode || m->cfg.expert_parallel || Q < 2 || Q > 4 || m->cfg.top_k > 8) return false;
+    if (!knobs().moe_deferred_merge || m->cfg.expert_parallel || Q < 2 || Q > 4 || m->cfg.top_k > 8) return false;
     const int P = T * m->cfg.top_k;
     // few pairs (block-major grid): every workgroup runs the full merge + align on a few hundred bytes of lists
     // (only where the gate_up launch is the K-split form — ≤ 16 pairs, c ≤ 2: c = 1 1.99 → 1.88 ms per step, c = 2 2.16 → 2.03.
     // In the one-wave-per-tile form every one of the ≈ 770 workgroups at c = 4 pays the merge: its launch 13.5 → 17.3 µs against
     // 2.9 µs saved in the chain; at c = 8 2.89 → 3.03 ms per step)
-    if (P <= std::min(knobs().moe_kw_pairs, 64) && T <= 4 && !moe_pair_form(m, L, P)) return true;
-    // expert-major merged launch: each tile only checks its own expert against the lists; measured at c = 32 the ≈ 8 KiB of lists
-    // read by all 7168 workgroups cost the launch what role B's merge cost the chain (47.4 → 50.3 µs vs ≈ −3 µs): off unless asked for
-    if (mode < 2) return false;
-    MoeRouteLists r;
-    r.cand = m->route_cand; r.stats = m->route_stats; r.T = T; r.Q = Q; r.pub_expert_ids = m->expert_ids; r.pub_expert_w = m->expert_w;
-    return moe_pair_form(m, L, P) && !L.exp_gate_up.perm && w4_gemm_moe_expert_major_pair_supports(L.exp_gate_up, L.exp_down, m->ep_E, P, &r);
+    return P <= std::min(knobs().moe_kw_pairs, 64) && T <= 4 && !moe_pair_form(m, L, P);
 }
 
 static int moe_decode_gemms(FerrumHipModel* m, LayerWeights& L, int P, int max_blocks, hipStream_t s, const MoeRouteLists* route = nullptr) {
@@ -1103,29 +1096,19 @@ static int moe_decode_gemms(FerrumHipModel* m, LayerWeights& L, int P, int max_b
     if (int rc = moe_gate_up_input(m, L, P / K, s, &gx)) return rc;
     // (the expert-major threshold compares pairs per expert: P pairs over num_experts, whatever share of them is local)
     if (m->moe_em_min_pairs_x8 > 0 && 8L * P >= (long)m->moe_em_min_pairs_x8 * c.num_experts) {
-        if (moe_pair_form(m, L, P)) {
+        if (!route && moe_pair_form(m, L, P)) {
             // one launch: down tiles wait for their expert's gate_up tiles inside it (w4_gemm_moe_em2_kernel)
             unsigned* cur = m->em2_arrive + (size_t)m->em2_parity * m->arrive_half_words;
             unsigned* nxt = m->em2_arrive + (size_t)(m->em2_parity ^ 1) * m->arrive_half_words;
             int took = 0;
             if (int rc = w4_gemm_moe_expert_major_pair(L.exp_gate_up, L.exp_down, gx, m->moe_act, m->moe_down, ids, E, P, K, cur, nxt,
-                                                       m->inlaunch_timeouts, &took, s, route)) return rc;
-            if (took) { m->em2_parity ^= 1; if (route) form_hit(FORM_MOE_DEFERRED_MERGE); return 0; }
+                                                       m->inlaunch_timeouts, &took, s)) return rc;
+            if (took) { m->em2_parity ^= 1; return 0; }
         }
-        FH_REQUIRE(!route, "MoE decode: the routing was left as candidate lists but the merged launch did not take the shapes");
+        FH_REQUIRE(!route, "MoE decode: the routing was left as candidate lists but the batch takes the expert-major form");
         if (int rc = w4_gemm_moe_expert_major(L.exp_gate_up, gx, m->moe_act, ids, E, P, K, 1, s)) return rc;
         if (int rc = moe_down_input(m, L, P, s, &hx)) return rc;
         return w4_gemm_moe_expert_major(L.exp_down, hx, m->moe_down, ids, E, P, 1, 0, s);
-    }
-    if (knobs().moe_bm2 && m->em2_arrive && !m->em2_failed && !L.exp_down.perm && max_blocks <= E &&
-        w4_gemm_moe_block_major_pair_supports(L.exp_gate_up, L.exp_down, E, P, max_blocks, route)) {
-        // ≤ 64 pairs: one block-major launch, down tiles wait for their block's gate_up tiles inside it (w4_gemm_moe_bm2_kernel)
-        unsigned* cur = m->em2_arrive + (size_t)m->em2_parity * m->arrive_half_words;
-        unsigned* nxt = m->em2_arrive + (size_t)(m->em2_parity ^ 1) * m->arrive_half_words;
-        int took = 0;
-        if (int rc = w4_gemm_moe_block_major_pair(L.exp_gate_up, L.exp_down, gx, m->moe_act, m->moe_down, ids, E, P, max_blocks, K, cur, nxt,
-                                                  m->inlaunch_timeouts, &took, s, route)) return rc;
-        if (took) { m->em2_parity ^= 1; if (route) form_hit(FORM_MOE_DEFERRED_MERGE); return 0; }
     }
     if (route) {
         // gate_up merges the lists, aligns, and publishes ids / weights / align arrays; down reads the align arrays
@@ -1151,59 +1134,39 @@ static int moe_batch_gemms(FerrumHipModel* m, LayerWeights& L, int P, int sorted
     const int E = m->ep_E, K = c.top_k, Eg = c.num_experts;     // block shapes are chosen by pairs per expert over ALL experts
     const int32_t* ids = moe_ids(m);
     const __half *gx = nullptr, *hx = nullptr;
-    if (P > 1024) FH_TRY(moe_gate_up_input(m, L, P / K, s, &gx));            // (decode-sized batches: moe_decode_gemms gathers for itself)
-    if (P <= 1024) {
-        FH_TRY(moe_decode_gemms(m, L, P, max_blocks, s));
-    } else if (P >= (long)m->moe_tile96_min_pairs_per_expert * Eg && L.exp_gate_up.G % 2 == 0 && L.exp_down.G % 2 == 0) {
+    if (P <= 1024) return moe_decode_gemms(m, L, P, max_blocks, s);
+    FH_TRY(moe_gate_up_input(m, L, P / K, s, &gx));
+    const bool even_groups = L.exp_gate_up.G % 2 == 0 && L.exp_down.G % 2 == 0;
+    int bs = 16;                     // align block size
+    if (P >= (long)m->moe_tile96_min_pairs_per_expert * Eg && even_groups) {
         // long prefill: 96-row blocks through w4_gemm_big_kernel<6> (two workgroups per CU; group scale folded into the fp16 B operand)
-        const int sorted_max96 = P + E * 96, max_blocks96 = std::min(sorted_max96 / 96, P / 96 + std::min(P, E));
-        FH_TRY(moe_align_block_size(ids, m->sorted_ids, m->block_ids, m->total_post_pad, P, E, 96, sorted_max96, s));
-        {
-            FH_TRY(w4_gemm_moe_tile(L.exp_gate_up, gx, m->moe_act, m->sorted_ids, m->block_ids, m->total_post_pad, P,
-                                 max_blocks96, 96, K, 1, s));
-        }
-        FH_TRY(moe_down_input(m, L, P, s, &hx));
-        FH_TRY(w4_gemm_moe_tile(L.exp_down, hx, m->moe_down, m->sorted_ids, m->block_ids, m->total_post_pad, P,
-                             max_blocks96, 96, 1, 0, s));
-    } else if (P >= (long)m->moe_tile128_min_pairs_per_expert * Eg && L.exp_gate_up.G % 2 == 0 && L.exp_down.G % 2 == 0) {
+        bs = 96;
+    } else if (P >= (long)m->moe_tile128_min_pairs_per_expert * Eg && even_groups) {
         // long prefill: 128-row blocks through w4_gemm_big_kernel (group scale folded into the fp16 B operand: the matrix pipe, not
         // vector issue, bounds it; twice the padding of 64-row blocks, hence only from a few hundred pairs per expert)
-        const int sorted_max128 = P + E * 128, max_blocks128 = std::min(sorted_max128 / 128, P / 128 + std::min(P, E));
-        FH_TRY(moe_align_block_size(ids, m->sorted_ids, m->block_ids, m->total_post_pad, P, E, 128, sorted_max128, s));
-        FH_TRY(w4_gemm_moe_tile(L.exp_gate_up, gx, m->moe_act, m->sorted_ids, m->block_ids, m->total_post_pad, P,
-                             max_blocks128, 128, K, 1, s));
-        FH_TRY(moe_down_input(m, L, P, s, &hx));
-        FH_TRY(w4_gemm_moe_tile(L.exp_down, hx, m->moe_down, m->sorted_ids, m->block_ids, m->total_post_pad, P,
-                             max_blocks128, 128, 1, 0, s));
+        bs = 128;
     } else if (P >= m->moe_tile_min_pairs_per_expert * Eg) {
         // prefill: ≥ 32 pairs per expert on average → 64-row blocks through the LDS-tiled kernel
-        const int sorted_max64 = P + E * 64, max_blocks64 = std::min(sorted_max64 / 64, P / 64 + std::min(P, E));
-        FH_TRY(moe_align_block_size(ids, m->sorted_ids, m->block_ids, m->total_post_pad, P, E, 64, sorted_max64, s));
-        FH_TRY(w4_gemm_moe_tile(L.exp_gate_up, gx, m->moe_act, m->sorted_ids, m->block_ids, m->total_post_pad, P,
-                             max_blocks64, 64, K, 1, s));
-        FH_TRY(moe_down_input(m, L, P, s, &hx));
-        FH_TRY(w4_gemm_moe_tile(L.exp_down, hx, m->moe_down, m->sorted_ids, m->block_ids, m->total_post_pad, P,
-                             max_blocks64, 64, 1, 0, s));
+        bs = 64;
     } else if (P >= m->moe_tile32_min_pairs_per_expert * Eg) {
         // a few hundred tokens (a fresh prompt riding along with the decode batch, a lone short prefill: 8–31 pairs
         // per expert): 32-row blocks through the LDS-tiled kernel — every expert's weights about once instead of
         // once per 16 pairs
-        const int sorted_max32 = P + E * 32, max_blocks32 = std::min(sorted_max32 / 32, P / 32 + std::min(P, E));
-        FH_TRY(moe_align_block_size(ids, m->sorted_ids, m->block_ids, m->total_post_pad, P, E, 32, sorted_max32, s));
-        FH_TRY(w4_gemm_moe_tile(L.exp_gate_up, gx, m->moe_act, m->sorted_ids, m->block_ids, m->total_post_pad, P,
-                             max_blocks32, 32, K, 1, s));
-        FH_TRY(moe_down_input(m, L, P, s, &hx));
-        FH_TRY(w4_gemm_moe_tile(L.exp_down, hx, m->moe_down, m->sorted_ids, m->block_ids, m->total_post_pad, P,
-                             max_blocks32, 32, 1, 0, s));
-    } else {
+        bs = 32;
+    }
+    if (bs == 16) {
         FH_TRY(moe_align_block_size(ids, m->sorted_ids, m->block_ids, m->total_post_pad, P, E, 16, sorted_max, s));
         FH_TRY(w4_gemm_moe(L.exp_gate_up, gx, m->moe_act, m->sorted_ids, m->block_ids, m->total_post_pad, P,
                         max_blocks, K, 1, s));
         FH_TRY(moe_down_input(m, L, P, s, &hx));
-        FH_TRY(w4_gemm_moe(L.exp_down, hx, m->moe_down, m->sorted_ids, m->block_ids, m->total_post_pad, P,
-                        max_blocks, 1, 0, s));
+        return w4_gemm_moe(L.exp_down, hx, m->moe_down, m->sorted_ids, m->block_ids, m->total_post_pad, P, max_blocks, 1, 0, s);
     }
-    return 0;
+    const int sorted_max_bs = P + E * bs, max_blocks_bs = std::min(sorted_max_bs / bs, P / bs + std::min(P, E));
+    FH_TRY(moe_align_block_size(ids, m->sorted_ids, m->block_ids, m->total_post_pad, P, E, bs, sorted_max_bs, s));
+    FH_TRY(w4_gemm_moe_tile(L.exp_gate_up, gx, m->moe_act, m->sorted_ids, m->block_ids, m->total_post_pad, P,
+                         max_blocks_bs, bs, K, 1, s));
+    FH_TRY(moe_down_input(m, L, P, s, &hx));
+    return w4_gemm_moe_tile(L.exp_down, hx, m->moe_down, m->sorted_ids, m->block_ids, m->total_post_pad, P, max_blocks_bs, bs, 1, 0, s);
 }
 #undef FH_TRY
 
@@ -2022,16 +1985,8 @@ int ferrum_hip_model_time_kernel(FerrumHipModel* m, int which, int n_seqs, int m
             unsigned* cur = m->em2_arrive + (size_t)(launches & 1) * m->arrive_half_words;
             unsigned* nxt = m->em2_arrive + (size_t)((launches & 1) ^ 1) * m->arrive_half_words;
             int took = 0;
-            // (as the step runs it: with the routing taken from the candidate lists the last forward's chain left behind)
-            int Q = m->route_parts;
-            const int tiles = (c.num_experts + 15) / 16;
-            while (Q > 1 && (tiles % Q != 0 || Q > 8)) Q >>= 1;
-            MoeRouteLists lists;
-            lists.cand = m->route_cand; lists.stats = m->route_stats; lists.T = T; lists.Q = Q; lists.norm_topk = c.norm_topk_prob;
-            lists.pub_expert_ids = m->expert_ids; lists.pub_expert_w = m->expert_w;
-            const bool defer = knobs().decode_chain && Q > 1 && moe_deferred_merge_ok(m, L, T, Q);
             if (int r_ = w4_gemm_moe_expert_major_pair(L.exp_gate_up, L.exp_down, m->norm_out, m->moe_act, m->moe_down, eids, E, P, c.top_k,
-                                                       cur, nxt, m->inlaunch_timeouts, &took, s, defer ? &lists : nullptr)) return r_;
+                                                       cur, nxt, m->inlaunch_timeouts, &took, s)) return r_;
             if (!took) { fh::set_error("time_kernel: the merged gate_up → down launch does not take these shapes"); return FERRUM_HIP_UNSUPPORTED; }
             return 0;
         }
