@@ -42,6 +42,7 @@ void reload_knobs() {
     k.moe_em2 = env_int("FERRUM_HIP_MOE_EM2", 1);
     k.decode_chain = env_int("FERRUM_HIP_DECODE_CHAIN", 1);
     k.moe_deferred_merge = env_int("FERRUM_HIP_MOE_DEFERRED_MERGE", 1);
+    k.moe_pair_rank_lists = env_int("FERRUM_HIP_MOE_PAIR_RANK_LISTS", 1);
     k.dense_chain = env_int("FERRUM_HIP_DENSE_CHAIN", 1);
     k.chain_max_keys = env_int("FERRUM_HIP_CHAIN_MAX_KEYS", 4096);
     k.chain_split_keys = env_int("FERRUM_HIP_CHAIN_SPLIT_KEYS", 256);
@@ -81,7 +82,8 @@ static const char* const g_form_names[FORM_COUNT] = {
     "moe_expert_major", "moe_inline_align", "moe_block16", "moe_tile64", "moe_tile32", "moe_tile_big", "moe_merge_route", "route_split",
     "route_fused", "route_gemm", "dense_slab_chain", "graph_capture", "graph_replay", "tp_allreduce_rccl",
     "tp_allreduce_loopback", "tp_allreduce_oneshot", "f16_dense_linear", "w4_fused_tail", "attn_resident", "w4_big", "gather_columns",
-    "perm_producer", "moe_expert_major_pair", "decode_chain", "moe_deferred_merge", "dense_chain", "tp_allreduce_norm_fused", "chain_attn_kv_splits", "chain_qkv_wide", "route_gemm_topk"};
+    "perm_producer", "moe_expert_major_pair", "decode_chain", "moe_deferred_merge", "dense_chain", "tp_allreduce_norm_fused", "chain_attn_kv_splits", "chain_qkv_wide", "route_gemm_topk",
+    "moe_pair_rank_lists"};
 const char* form_name(int f) { return f >= 0 && f < FORM_COUNT ? g_form_names[f] : nullptr; }
 }  // namespace fh
 

@@ -125,7 +125,7 @@ __device__ __forceinline__ void chain_wait(unsigned* base, int shards, int reps,
             if (__ballot(c < need) == 0ull) break;
             __builtin_amdgcn_s_sleep(4);
             if ((++spins & 255u) == 0u && wall_clock64() - t0 > 2000000ull) {
-                if (lane == 0) __hip_atomic_fetch_add(timeout, 1u, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_SYSTEM);
+                if (lane == 0) __hip_atomic_fetch_add(timeout, INLAUNCH_GAVE_UP_CHAIN, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_SYSTEM);
                 break;
             }
         }
@@ -649,8 +649,7 @@ __device__ __forceinline__ void chain_role_b(const ChainArgs& p, int wg, unsigne
         wv_pre[c] = *reinterpret_cast<const half8*>(p.post_ln + (i < nvec ? i : 0) * 8);
     }
     constexpr int U = 16;
-    const int tiles = (num_experts + 15) >> 4;
-    const int tiles_q = num_experts > 0 ? tiles / Q : 0;              // (dense model: no router, Q = 1)
+    const int tiles_q = num_experts > 0 ? moe_route_part_tiles(num_experts, Q) : 0;      // (dense model: no router, Q = 1)
     const int ksplit = (tiles_q >= 8 || tiles_q == 0) ? 1 : 8 / tiles_q;
     const int ksteps = H >> 5;
     half8 bw_pre[U];
@@ -791,7 +790,8 @@ __device__ __forceinline__ void chain_role_b(const ChainArgs& p, int wg, unsigne
     if (wave != 0) return;
     if (p.defer_merge) {
         // the consumer is the NEXT launch (the grouped gate_up GEMM merges the Q lists of every token in its prologue, under its
-        // first weight loads): plain stores, no meeting of the parts here — the ≈ 3.7 µs merge leaves the layer's critical path
+        // first weight loads — or, where the layer's grouped GEMMs are the expert pair, every tile of it ranks its own expert's
+        // candidates): plain stores, no meeting of the parts here — the ≈ 3.7 µs merge leaves the layer's critical path
         unsigned long long* cand_g = reinterpret_cast<unsigned long long*>(p.cand) + (row * Q + q) * 8;
         if (lane < 8) cand_g[lane] = cand_s[lane];
         if (lane == 8) reinterpret_cast<unsigned long long*>(p.stats)[row * Q + q] =
@@ -828,7 +828,7 @@ __device__ __forceinline__ void chain_role_b(const ChainArgs& p, int wg, unsigne
             if (__ballot(!have) == 0ull) break;
             __builtin_amdgcn_s_sleep(1);
             if ((++spins & 1023u) == 0u && wall_clock64() - t0 > 2000000ull) {
-                if (lane == 0) __hip_atomic_fetch_add(p.timeout, 1u, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_SYSTEM);
+                if (lane == 0) __hip_atomic_fetch_add(p.timeout, INLAUNCH_GAVE_UP_CHAIN, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_SYSTEM);
                 break;
             }
         }

@@ -63,8 +63,17 @@ int w4_gemm_moe_expert_major(const W4Device& w, const __half* x, __half* out, co
 // words between the per-expert arrival counters of the merged launch (one 256-byte line each): `arrive` / `arrive_next` hold
 // num_experts · MOE_PAIR_COUNTER_STRIDE words
 constexpr int MOE_PAIR_COUNTER_STRIDE = 64;
+// what a bounded in-launch wait that gave up adds to the host-visible give-up word: the low half counts the expert pair's
+// waits (gate_up → down hand-off), the high half the decode chain's (role hand-offs, router parts) — the host names the kernel
+constexpr unsigned INLAUNCH_GAVE_UP_PAIR = 1u, INLAUNCH_GAVE_UP_CHAIN = 1u << 16;
 // routing handed over as the router's Q per-part candidate lists of every token (fused.hip part kernel / chain.hip role B
 // with defer_merge) instead of merged pair ids: the grouped GEMM merges them in its prologue and publishes ids + combine weights
+// How the router's parts split the experts (chain.hip role B, and every reader of its lists): whole 16-expert tiles, the
+// same number to every part — part q is experts [q, q + 1) · moe_route_part_experts, cut at E (E need not fill the last tile)
+__host__ __device__ inline int moe_route_part_tiles(int num_experts, int Q) { return ((num_experts + 15) >> 4) / Q; }
+__host__ __device__ inline int moe_route_part_experts(int num_experts, int Q) { return moe_route_part_tiles(num_experts, Q) * 16; }
+// the runner's list buffers: this many (token, part) lists of 8 candidates (route_cand), and as many (max, Σexp) pairs (route_stats)
+constexpr int MOE_ROUTE_LIST_CAPACITY = 512;
 struct MoeRouteLists {
     const RouteCand* cand = nullptr; const float* stats = nullptr;
     int T = 0, Q = 0, norm_topk = 0;
@@ -73,7 +82,12 @@ struct MoeRouteLists {
 bool w4_gemm_moe_expert_major_pair_supports(const W4Device& gu, const W4Device& dn, int num_experts, int num_valid_pairs);
 int w4_gemm_moe_expert_major_pair(const W4Device& gu, const W4Device& dn, const __half* x, __half* h, __half* out,
                                   const int32_t* pair_expert_ids, int num_experts, int num_valid_pairs, int top_k,
-                                  unsigned* arrive, unsigned* arrive_next, unsigned* timeout, int* took, hipStream_t stream);
+                                  unsigned* arrive, unsigned* arrive_next, unsigned* timeout, int* took, hipStream_t stream,
+                                  const MoeRouteLists* lists = nullptr);
+// `lists`: the routing as per-part candidate lists instead of pair_expert_ids — every tile finds its expert's rows in them
+// (its own part's lists, then a rank lookup in the other parts' for the tokens that have it), the expert's first gate_up
+// tile publishes the pairs' ids and combine weights (lists->pub_*): what the in-chain merge would have written
+bool w4_gemm_moe_expert_major_pair_takes_lists(const MoeRouteLists& lists, int num_experts, int num_valid_pairs, int top_k);
 int w4_gemm_moe_inline_align(const W4Device& w, const __half* x, __half* out, const int32_t* pair_expert_ids,
                              int num_experts, int num_valid_pairs, int max_blocks, int top_k, int fused_silu,
                              int32_t* pub_sorted, int32_t* pub_block_ids, int32_t* pub_total, hipStream_t stream,
@@ -245,7 +259,7 @@ struct DecodeChainDesc {
     const W4Device* o = nullptr; __half* o_out = nullptr;
     __half* res_b_out = nullptr; const __half* post_ln = nullptr; __half* norm2 = nullptr; const __half* router_w = nullptr;
     int E = 0, r_top_k = 0, Q = 0, norm_topk = 0;
-    bool defer_merge = false;    // role B stops at the per-part candidate lists (cand / stats); the grouped GEMM that follows merges them
+    bool defer_merge = false;    // role B stops at the per-part candidate lists (cand / stats); the grouped GEMM that follows merges them (or looks its rows up in them: the expert pair)
     RouteCand* cand = nullptr; float* stats = nullptr; unsigned* route_arrive = nullptr; int32_t* ids = nullptr; float* weights = nullptr;
     float* o_part = nullptr;       // [2][T][H] fp32: o_proj's two K parts (one workgroup each per block; role B adds them)
     int attn_splits = 1;           // KV ranges per (sequence, kv head) in the attention role (≤ 16); > 1 needs the two buffers below

@@ -41,6 +41,7 @@ struct Knobs {
     int dense_chain = 1;              // dense models at 17–32 rows: the attention half of the layer as the chain launch too (0 = five launches)
     int moe_em2 = 1;                  // decode: gate_up → down as one expert-major launch (0 = two launches)
     int moe_deferred_merge = 1;       // decode chain: the grouped GEMM's prologue merges the router's candidate lists (0 = role B does)
+    int moe_pair_rank_lists = 1;      // decode chain + expert pair: the pair's tiles resolve their rows from the candidate lists (0 = role B merges)
     int w4_tile_min_m = 0;
     int w4_tile_wgs = 256;
     int w4_ldsa = 1;
@@ -107,6 +108,7 @@ enum Form : int {
     FORM_CHAIN_ATTN_KV_SPLITS,  // decode chain with several KV ranges per (sequence, kv head) in its attention role (ticket merge)
     FORM_CHAIN_QKV_WIDE,        // decode chain with 128-column q|k|v blocks (the narrow ones + attention exceed the resident workgroups)
     FORM_ROUTE_GEMM_TOPK,       // prefill router: logits (MFMA) + softmax + top-k in one launch (moe_route_gemm_topk_kernel)
+    FORM_MOE_PAIR_RANK_LISTS,   // the expert pair took the routing as per-part candidate lists: each tile ranks its own expert's candidates
     FORM_COUNT
 };
 

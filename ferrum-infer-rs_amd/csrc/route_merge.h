@@ -8,6 +8,10 @@
 
 namespace fh {
 
+// The selection order as one predicate: does candidate (lj, ij) come before candidate (l, id)?  Every merge below and the
+// expert pair's own rank lookup (route_rank_in_lists) use this and nothing else, so they cannot disagree on a tie.
+__device__ __forceinline__ bool route_beats(float lj, int ij, float l, int id) { return lj > l || (lj == l && ij < id); }
+
 // Lanes [0, ncand) hold one candidate each, c = (expert id << 32) | logit bits (an unused slot: id 0x7fffffff, logit −inf),
 // lanes [0, Q) the statistics of part `lane`.  Returns the lane's rank in the merged order; `weight` (only when
 // want_weights, a wave-uniform flag) is the lane's combine weight if rank < top_k.
@@ -20,7 +24,7 @@ __device__ __forceinline__ int route_merge_token(unsigned long long c, int ncand
     for (int j = 0; j < ncand; j++) {
         const float lj = __uint_as_float(__builtin_amdgcn_readlane((int)(unsigned)c, j));
         const int ij = __builtin_amdgcn_readlane((int)(c >> 32), j);
-        rank += (lj > my_l || (lj == my_l && ij < my_id)) ? 1 : 0;
+        rank += route_beats(lj, ij, my_l, my_id) ? 1 : 0;
     }
     if (want_weights) {
         const float gmax = wave_reduce_max(lane < Q ? pmx : -INFINITY);
@@ -66,7 +70,7 @@ __device__ __forceinline__ int route_merge_pair(unsigned long long c, int Q, int
 #pragma unroll
         for (int d = 0; d < 3; d++) {
             const bool act = lo[d] < hi[d];
-            const bool beats = lj[d] > my_l || (lj[d] == my_l && ij[d] < my_id);
+            const bool beats = route_beats(lj[d], ij[d], my_l, my_id);
             if (act && beats) lo[d] = mid[d] + 1;
             if (act && !beats) hi[d] = mid[d];
         }
@@ -75,6 +79,25 @@ __device__ __forceinline__ int route_merge_pair(unsigned long long c, int Q, int
 #pragma unroll
     for (int d = 0; d < 3; d++) rank += d + 1 < Q ? lo[d] : 0;
     return rank;
+}
+
+// One (token, expert) lookup for a grouped GEMM tile that owns expert `id`: the candidate's merged rank is the number of
+// candidates in ALL of the token's Q lists that come before it — its own list is sorted by the same order, so that part of
+// the count is its slot there, and the rest is route_merge_pair's prefix lengths (the lists are sorted: a prefix length is a
+// count).  Four lanes per lookup, lane `sub` counts through part `sub`'s list (`list`: its 8 entries as four 16-byte loads,
+// {logit, id} pairs); the four counts meet by two lane swaps.  Every lane of the group returns the rank.
+typedef uint32_t route_u32x4 __attribute__((ext_vector_type(4)));
+__device__ __forceinline__ int route_rank_in_lists(const route_u32x4 (&list)[4], bool part_valid, float l, int id) {
+    int cnt = 0;
+#pragma unroll
+    for (int k = 0; k < 4; k++) {
+        cnt += route_beats(__uint_as_float(list[k].x), (int)list[k].y, l, id) ? 1 : 0;
+        cnt += route_beats(__uint_as_float(list[k].z), (int)list[k].w, l, id) ? 1 : 0;
+    }
+    cnt = part_valid ? cnt : 0;
+    cnt += __shfl_xor(cnt, 1, 64);
+    cnt += __shfl_xor(cnt, 2, 64);
+    return cnt;
 }
 
 // combine weight of the lane's candidate (valid where rank < top_k); st = the token's (max, Σexp) statistics, Q pairs

@@ -79,7 +79,7 @@ struct FerrumHipModel {
     float* chain_o_part = nullptr;        // decode chain: o_proj's two K parts, [2][128][H] fp32
     float* chain_attn_partial = nullptr;  // decode chain, attention role with KV splits: [≤ 1024 (unit, split)][16][head_dim + 4] states
     unsigned* chain_attn_tickets = nullptr;   // [4096] one self-resetting ticket per (sequence, kv head)
-    fh::RouteCand* route_cand = nullptr;  // [T ≤ 64][Q][8]
+    fh::RouteCand* route_cand = nullptr;  // [T][Q][8], T · Q ≤ MOE_ROUTE_LIST_CAPACITY
     float* route_stats = nullptr;         // [T][Q][2]
     unsigned* route_arrive = nullptr;     // [T] arrival counters of the split route kernel (zero between launches)
     unsigned* em2_arrive = nullptr;       // [2][E] per-expert arrival counters of the merged gate_up → down launch (double buffer: each launch zeroes the other half) + [1] give-up count

@@ -289,8 +289,10 @@ static int check_inlaunch_waits(FerrumHipModel* m) {
     m->inlaunch_timeouts_seen = now;
     m->em2_failed = true;
     drop_graph(m);
-    fh::set_error("%u in-launch wait(s) of a merged kernel gave up (gate_up → down hand-off): the results of this call are invalid; "
-                  "the two-launch form is used from now on", n);
+    const unsigned n_pair = n & 0xffffu, n_chain = n >> 16;
+    fh::set_error("in-launch waits of the merged kernels gave up — w4_gemm_moe_em2_kernel (gate_up → down hand-off): %u, "
+                  "decode_chain_kernel (role hand-offs): %u: the results of this call are invalid; the multi-launch layer is used "
+                  "from now on", n_pair, n_chain);
     return 3;
 }
 
@@ -776,8 +778,10 @@ int ferrum_hip_model_finalize(FerrumHipModel* m) {
         rc |= dev_alloc(&m->block_ids, sorted_max / 16 + 1);
         rc |= dev_alloc(&m->total_post_pad, (size_t)4);
         rc |= dev_alloc(&m->residual2, (size_t)128 * H);
-        rc |= dev_alloc(&m->route_cand, (size_t)512 * 8);     // [T ≤ 64][Q ≤ 8][8]
-        rc |= dev_alloc(&m->route_stats, (size_t)512 * 2);
+        // the router's candidate lists: [T][Q][8] and [T][Q][2] — every form that writes them checks T · Q against the capacity
+        // (the split route kernel: ≤ 64 rows of ≤ 8 parts; the chain's deferred forms: moe_deferred_merge_ok, moe_pair_rank_lists_ok)
+        rc |= dev_alloc(&m->route_cand, (size_t)MOE_ROUTE_LIST_CAPACITY * 8);
+        rc |= dev_alloc(&m->route_stats, (size_t)MOE_ROUTE_LIST_CAPACITY * 2);
         // [64] arrival counters of the split route kernel (zeroed here; the kernel re-arms them) + [2][E] per-expert counters of the
         // merged gate_up → down launch + its give-up count; the head kernel of every forward zeroes the route counters and half 0
         // layout: route [64] | pair half 0 | chain half 0 | pair half 1 | chain half 1
@@ -1022,6 +1026,15 @@ int ferrum_hip_model_read_taps(FerrumHipModel* m, float* out_host, int max_token
                                (size_t)T * m->cfg.hidden * 4, hipMemcpyDeviceToHost));
     return 0;
 }
+int ferrum_hip_model_read_routing(FerrumHipModel* m, int32_t* ids_host, float* weights_host, int pairs) {
+    FH_REQUIRE(m && m->finalized && ids_host && weights_host, "model_read_routing: bad state");
+    FH_REQUIRE(m->expert_ids && m->expert_w && pairs >= 1 && pairs <= m->cfg.max_tokens * std::max(m->cfg.top_k, 1),
+               "model_read_routing: not a MoE model, or pairs=%d out of range", pairs);
+    FH_CHECK_HIP(hipStreamSynchronize(m->stream));
+    FH_CHECK_HIP(hipMemcpy(ids_host, m->expert_ids, (size_t)pairs * 4, hipMemcpyDeviceToHost));
+    FH_CHECK_HIP(hipMemcpy(weights_host, m->expert_w, (size_t)pairs * 4, hipMemcpyDeviceToHost));
+    return 0;
+}
 int ferrum_hip_model_stream(FerrumHipModel* m, void** stream) {
     FH_REQUIRE(m && stream, "model_stream: null");
     *stream = m->stream;
@@ -1080,12 +1093,34 @@ static bool moe_pair_form(const FerrumHipModel* m, const LayerWeights& L, int P)
 }
 static bool moe_deferred_merge_ok(const FerrumHipModel* m, const LayerWeights& L, int T, int Q) {
     if (!knobs().moe_deferred_merge || m->cfg.expert_parallel || Q < 2 || Q > 4 || m->cfg.top_k > 8) return false;
+    if ((long)T * Q > MOE_ROUTE_LIST_CAPACITY) return false;
     const int P = T * m->cfg.top_k;
     // few pairs (block-major grid): every workgroup runs the full merge + align on a few hundred bytes of lists
     // (only where the gate_up launch is the K-split form — ≤ 16 pairs, c ≤ 2: c = 1 1.99 → 1.88 ms per step, c = 2 2.16 → 2.03.
     // In the one-wave-per-tile form every one of the ≈ 770 workgroups at c = 4 pays the merge: its launch 13.5 → 17.3 µs against
     // 2.9 µs saved in the chain; at c = 8 2.89 → 3.03 ms per step)
     return P <= std::min(knobs().moe_kw_pairs, 64) && T <= 4 && !moe_pair_form(m, L, P);
+}
+
+// router parts per token in the chain's role B
+static int chain_route_parts(const FerrumHipModel* m) {
+    if (m->cfg.num_experts <= 0) return 1;
+    int Q = m->route_parts;
+    const int tiles = (m->cfg.num_experts + 15) / 16;
+    while (Q > 1 && (tiles % Q != 0 || Q > 8)) Q >>= 1;
+    return Q;
+}
+// The expert pair resolves its rows from the lists itself (w4_gemm_moe_em2_kernel<…, LISTS>): wherever the pair is the batch's
+// form, the lists have the geometry its lookup takes and the list buffers hold them.  Decided BEFORE the chain launch, like
+// the deferred merge: role B then stops at the lists and the ≈ 3.7 µs in-launch merge leaves the layer.
+static bool moe_pair_rank_lists_ok(const FerrumHipModel* m, const LayerWeights& L, int T, int Q) {
+    if (!knobs().moe_pair_rank_lists || m->cfg.expert_parallel || !m->route_cand || !m->route_stats) return false;
+    if ((long)T * Q > MOE_ROUTE_LIST_CAPACITY) return false;
+    const int P = T * m->cfg.top_k;
+    MoeRouteLists l;
+    l.cand = m->route_cand; l.stats = m->route_stats; l.T = T; l.Q = Q; l.pub_expert_ids = m->expert_ids; l.pub_expert_w = m->expert_w;
+    return moe_pair_form(m, L, P) && w4_gemm_moe_expert_major_pair_supports(L.exp_gate_up, L.exp_down, m->ep_E, P) &&
+           w4_gemm_moe_expert_major_pair_takes_lists(l, m->ep_E, P, m->cfg.top_k);
 }
 
 static int moe_decode_gemms(FerrumHipModel* m, LayerWeights& L, int P, int max_blocks, hipStream_t s, const MoeRouteLists* route = nullptr) {
@@ -1096,13 +1131,13 @@ static int moe_decode_gemms(FerrumHipModel* m, LayerWeights& L, int P, int max_b
     if (int rc = moe_gate_up_input(m, L, P / K, s, &gx)) return rc;
     // (the expert-major threshold compares pairs per expert: P pairs over num_experts, whatever share of them is local)
     if (m->moe_em_min_pairs_x8 > 0 && 8L * P >= (long)m->moe_em_min_pairs_x8 * c.num_experts) {
-        if (!route && moe_pair_form(m, L, P)) {
+        if (moe_pair_form(m, L, P)) {
             // one launch: down tiles wait for their expert's gate_up tiles inside it (w4_gemm_moe_em2_kernel)
             unsigned* cur = m->em2_arrive + (size_t)m->em2_parity * m->arrive_half_words;
             unsigned* nxt = m->em2_arrive + (size_t)(m->em2_parity ^ 1) * m->arrive_half_words;
             int took = 0;
             if (int rc = w4_gemm_moe_expert_major_pair(L.exp_gate_up, L.exp_down, gx, m->moe_act, m->moe_down, ids, E, P, K, cur, nxt,
-                                                       m->inlaunch_timeouts, &took, s)) return rc;
+                                                       m->inlaunch_timeouts, &took, s, route)) return rc;
             if (took) { m->em2_parity ^= 1; return 0; }
         }
         FH_REQUIRE(!route, "MoE decode: the routing was left as candidate lists but the batch takes the expert-major form");
@@ -1245,10 +1280,7 @@ int enqueue_forward(FerrumHipModel* m, const StepShape& sh, bool greedy, const G
         d.attn_out = m->attn_out; d.o = &L.o; d.o_out = m->o_out; d.o_part = m->chain_o_part;
         d.res_b_out = m->residual2; d.post_ln = L.post_ln; d.norm2 = m->norm_out; d.router_w = L.router;
         d.E = c.num_experts; d.r_top_k = c.top_k; d.norm_topk = c.norm_topk_prob;
-        int Q = m->route_parts;
-        const int tiles = (c.num_experts + 15) / 16;
-        while (Q > 1 && (tiles % Q != 0 || Q > 8)) Q >>= 1;
-        d.Q = c.num_experts > 0 ? Q : 1;
+        d.Q = chain_route_parts(m);
         d.cand = m->route_cand; d.stats = m->route_stats; d.route_arrive = m->route_arrive; d.ids = m->expert_ids; d.weights = m->expert_w;
         d.timeout = m->inlaunch_timeouts;
         // KV ranges per (sequence, kv head) in the attention role: ≈ chain_split_keys (256) keys each while the role stays within
@@ -1358,7 +1390,8 @@ int enqueue_forward(FerrumHipModel* m, const StepShape& sh, bool greedy, const G
             d.cnt_next = m->em2_arrive + (size_t)(m->chain_parity ^ 1) * m->arrive_half_words + (size_t)c.num_experts * MOE_PAIR_COUNTER_STRIDE;
             // the Q candidate lists of a token are merged by the grouped GEMM's prologue (under its first weight loads) where that
             // form runs, instead of by role B's first part at the end of the chain (≈ 3.7 µs of every layer)
-            d.defer_merge = d.Q > 1 && moe_deferred_merge_ok(m, L, T, d.Q);
+            // … or, where the layer's grouped GEMMs are the expert pair, looked up by each of its tiles for its own expert
+            d.defer_merge = d.Q > 1 && (moe_deferred_merge_ok(m, L, T, d.Q) || moe_pair_rank_lists_ok(m, L, T, d.Q));
             MoeRouteLists lists;
             lists.cand = m->route_cand; lists.stats = m->route_stats; lists.T = T; lists.Q = d.Q; lists.norm_topk = c.norm_topk_prob;
             lists.pub_expert_ids = m->expert_ids; lists.pub_expert_w = m->expert_w;
@@ -1985,8 +2018,13 @@ int ferrum_hip_model_time_kernel(FerrumHipModel* m, int which, int n_seqs, int m
             unsigned* cur = m->em2_arrive + (size_t)(launches & 1) * m->arrive_half_words;
             unsigned* nxt = m->em2_arrive + (size_t)((launches & 1) ^ 1) * m->arrive_half_words;
             int took = 0;
+            // (as the step runs it: from the candidate lists the last chain launch left, where that is the layer's form)
+            MoeRouteLists lists;
+            lists.cand = m->route_cand; lists.stats = m->route_stats; lists.T = T; lists.Q = chain_route_parts(m); lists.norm_topk = c.norm_topk_prob;
+            lists.pub_expert_ids = m->expert_ids; lists.pub_expert_w = m->expert_w;
+            const bool from_lists = lists.Q > 1 && knobs().decode_chain && moe_pair_rank_lists_ok(m, L, T, lists.Q);
             if (int r_ = w4_gemm_moe_expert_major_pair(L.exp_gate_up, L.exp_down, m->norm_out, m->moe_act, m->moe_down, eids, E, P, c.top_k,
-                                                       cur, nxt, m->inlaunch_timeouts, &took, s)) return r_;
+                                                       cur, nxt, m->inlaunch_timeouts, &took, s, from_lists ? &lists : nullptr)) return r_;
             if (!took) { fh::set_error("time_kernel: the merged gate_up → down launch does not take these shapes"); return FERRUM_HIP_UNSUPPORTED; }
             return 0;
         }

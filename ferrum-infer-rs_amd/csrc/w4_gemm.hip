@@ -768,6 +768,12 @@ struct W4Em2Args {
 #ifdef FERRUM_HIP_EXPERIMENTS
     unsigned long long* tl;          // development: per-wave wall-clock stamps (tools/exp_timeline_moe.py)
 #endif
+    // LISTS: the routing arrives as the router's per-part candidate lists (chain.hip role B, defer_merge) and every tile
+    // resolves its own expert's rows from them; pair_expert_ids / pub_w are then OUTPUTS (written by each expert's first tile)
+    const RouteCand* cand;           // [T][Q][8] sorted lists
+    const float* stats;              // [T][Q] (max, Σexp)
+    int route_Q, route_EQ, norm_topk; // parts per token, experts per part (moe_route_part_experts: role B's split, whole 16-expert tiles)
+    int32_t* pub_ids; float* pub_w;  // [P]
 };
 // Thousands of waves poll 128 counters: packed into 512 bytes they would all sit behind one or two memory channels (polls
 // and arrivals queue up behind each other there — the first build of this kernel took 108 µs instead of 50); one counter per
@@ -779,7 +785,7 @@ constexpr int EM2_STRIDE = MOE_PAIR_COUNTER_STRIDE;
 #define FH_TL2(i) do {} while (0)
 #endif
 
-template <bool HAS_ZP, bool IS_GU>
+template <bool HAS_ZP, bool IS_GU, bool LISTS>
 __device__ __forceinline__ void w4_em2_role(const W4Em2Args& p, int tile, int* s_rows, _Float16* s_out) {
     const int lane = threadIdx.x;
     const int a = lane >> 4, b = lane & 15;
@@ -805,19 +811,57 @@ __device__ __forceinline__ void w4_em2_role(const W4Em2Args& p, int tile, int* s
     if (IS_GU && st == 0 && lane == 0) p.arrive_next[e * EM2_STRIDE] = 0u;
     FH_TL2(0);
     int ids[16];
-    const int P = p.P, chunks = (P + 63) >> 6;
+    const int P = p.P;
+    // LISTS: the id words of the lists of the expert's own router part, entry t·8 + slot (T ≤ 128 tokens: ≤ 1024 entries)
+    const int Q = LISTS ? p.route_Q : 1, q = LISTS ? e / p.route_EQ : 0;
+    const uint32_t* cw = reinterpret_cast<const uint32_t*>(p.cand);          // RouteCand {logit, id}: even words logits, odd words ids
+    const int n_scan = LISTS ? P / p.top_k * 8 : P, chunks = (n_scan + 63) >> 6;
 #pragma unroll
-    for (int i = 0; i < 16; i++) ids[i] = (i < chunks && i * 64 + lane < P) ? p.pair_expert_ids[i * 64 + lane] : -1;
+    for (int i = 0; i < 16; i++) {
+        const int x = i * 64 + lane;
+        if constexpr (LISTS) ids[i] = (i < chunks && x < n_scan) ? (int)cw[(((x >> 3) * Q + q) * 8 + (x & 7)) * 2 + 1] : -1;
+        else ids[i] = (i < chunks && x < n_scan) ? p.pair_expert_ids[x] : -1;
+    }
     issue_w(0, 0);
     if (!IS_GU) issue_w(1, 1);         // (down: G ≥ 2, checked by the launcher) both ring slots are on their way before the wait
     __builtin_amdgcn_sched_barrier(0);
+    int* s_hit = LISTS ? s_rows + 512 : s_rows;       // LISTS: the tokens that have the expert as a candidate of its part (≤ 128 of 512 slots)
     int n_e = 0;
 #pragma unroll
     for (int i = 0; i < 16; i++) {
         if (i < chunks) {
             const bool mine = ids[i] == e;
             const unsigned long long bal = __ballot(mine);
-            if (mine) s_rows[n_e + __popcll(bal & ((1ull << lane) - 1ull))] = i * 64 + lane;
+            const int slot = n_e + __popcll(bal & ((1ull << lane) - 1ull));
+            if (mine && (!LISTS || slot < 512)) s_hit[slot] = i * 64 + lane;
+            n_e += __popcll(bal);
+        }
+    }
+    if constexpr (LISTS) {
+        // A candidate of its part is a pair of the expert when fewer than top_k candidates of the token come before it: sixteen
+        // tokens per pass, four lanes each (route_rank_in_lists) — one more round of loads from L2, behind the weight requests
+        // above.  Tokens ascend through the hit list, so the rows do (a token has the expert once): s_rows as the id scan fills it.
+        // (a token's list names an expert once: ≤ T hits.  Lists that are no router's output — time_kernel before any chain
+        // launch — may name it in every entry: the hit list keeps to its half of s_rows)
+        const int n_hit = n_e < 512 ? n_e : 512;
+        n_e = 0;
+        if (n_hit == 0) return;
+        __builtin_amdgcn_fence(__ATOMIC_RELEASE, "workgroup");
+        __builtin_amdgcn_wave_barrier();
+        const int sub = lane & 3;
+        for (int m0 = 0; m0 < n_hit; m0 += 16) {
+            const int mi = m0 + (lane >> 2);
+            const bool have = mi < n_hit;
+            const int x = s_hit[have ? mi : m0], t = x >> 3;
+            const float my_l = __uint_as_float(cw[((t * Q + q) * 8 + (x & 7)) * 2]);
+            const route_u32x4* lp = reinterpret_cast<const route_u32x4*>(cw + (long)(t * Q + (sub < Q ? sub : 0)) * 16);
+            route_u32x4 lv[4];
+#pragma unroll
+            for (int k = 0; k < 4; k++) lv[k] = lp[k];
+            const int rank = route_rank_in_lists(lv, sub < Q, my_l, e);
+            const bool sel = have && sub == 0 && rank < p.top_k;
+            const unsigned long long bal = __ballot(sel);
+            if (sel) s_rows[n_e + __popcll(bal & ((1ull << lane) - 1ull))] = t * p.top_k + rank;
             n_e += __popcll(bal);
         }
     }
@@ -890,6 +934,25 @@ __device__ __forceinline__ void w4_em2_role(const W4Em2Args& p, int tile, int* s
         asm volatile("s_waitcnt vmcnt(0)" ::: "memory");
         if (lane == 0) __hip_atomic_fetch_add(p.arrive + e * EM2_STRIDE, 1u, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT);
         FH_TL2(3);
+        if constexpr (LISTS) {
+            // The expert's first tile publishes its pairs' ids and combine weights for the launches behind this one (nothing in
+            // this launch reads them, so it comes last, behind the arrival): two tokens per pass with the merge and the weight
+            // arithmetic of the deferred form.  Every pair belongs to exactly one expert with rows: both arrays end up complete.
+            if (st == 0) {
+                const int half = lane >> 5, li = lane & 31, ncand = Q * 8;
+                const unsigned long long* cg = reinterpret_cast<const unsigned long long*>(p.cand);
+                for (int r0 = 0; r0 < n_e; r0 += 2) {
+                    const bool have = r0 + half < n_e;
+                    const int t = s_rows[have ? r0 + half : r0] / p.top_k;
+                    const bool valid = have && li < ncand;
+                    const unsigned long long c = valid ? cg[t * ncand + li] : ((0x7fffffffull << 32) | 0xff800000ull);
+                    int id;
+                    const int rank = route_merge_pair(c, Q, &id);
+                    const float ww = route_merge_pair_weight(c, rank, valid, p.stats + (long)t * Q * 2, Q, p.top_k, p.norm_topk);
+                    if (valid && id == e && rank < p.top_k) { p.pub_ids[t * p.top_k + rank] = e; p.pub_w[t * p.top_k + rank] = ww; }
+                }
+            }
+        }
     } else {
         // down: wait for the expert's gate_up tiles (bounded: ≈ 20 ms of the 100 MHz wall clock)
         {
@@ -904,7 +967,7 @@ __device__ __forceinline__ void w4_em2_role(const W4Em2Args& p, int tile, int* s
                 if (c + 4 < need) __builtin_amdgcn_s_sleep(64);
                 else __builtin_amdgcn_s_sleep(8);
                 if ((++spins & 63u) == 0u && wall_clock64() - t0 > 2000000ull) {
-                    if (lane == 0) __hip_atomic_fetch_add(p.timeout, 1u, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_SYSTEM);
+                    if (lane == 0) __hip_atomic_fetch_add(p.timeout, INLAUNCH_GAVE_UP_PAIR, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_SYSTEM);
                     break;
                 }
             }
@@ -982,13 +1045,13 @@ __device__ __forceinline__ void w4_em2_role(const W4Em2Args& p, int tile, int* s
 
 // (three waves per SIMD are what keeps all gate_up tiles resident: without the attribute the two inlined roles take 154 + 36
 // registers — two waves per SIMD; with it 168, and one 8-byte spill in the prologue, outside every loop)
-template <bool HAS_ZP>
+template <bool HAS_ZP, bool LISTS = false>
 __global__ __launch_bounds__(64) __attribute__((amdgpu_waves_per_eu(3, 3))) void w4_gemm_moe_em2_kernel(W4Em2Args p) {
     __shared__ __attribute__((aligned(16))) int s_rows[1024];
     __shared__ __attribute__((aligned(16))) _Float16 s_out[16 * 64];     // the tile's output rows, for 16-byte stores
     const int n_gu = p.gu_n64 * p.E, n_dn = p.dn_n64 * p.E;
-    if ((int)blockIdx.x < n_gu) { w4_em2_role<HAS_ZP, true>(p, blockIdx.x, s_rows, s_out); return; }
-    if ((int)blockIdx.x < n_gu + n_dn) w4_em2_role<HAS_ZP, false>(p, blockIdx.x - n_gu, s_rows, s_out);
+    if ((int)blockIdx.x < n_gu) { w4_em2_role<HAS_ZP, true, LISTS>(p, blockIdx.x, s_rows, s_out); return; }
+    if ((int)blockIdx.x < n_gu + n_dn) w4_em2_role<HAS_ZP, false, LISTS>(p, blockIdx.x - n_gu, s_rows, s_out);
 }
 
 // Sum S fp32 slabs in fixed order → fp16 [M, N] (optionally gathering padded MoE rows).
@@ -2358,15 +2421,28 @@ bool w4_gemm_moe_expert_major_pair_supports(const W4Device& gu, const W4Device& 
     return true;
 }
 
+// … with the routing as candidate lists (`lists`): the lists' geometry the tiles' lookup takes — Q sorted 8-entry lists per
+// token, part q over experts [q, q + 1) · moe_route_part_experts (the last part may be short: E need not be a multiple of
+// 16 · Q), every pair slot of a token filled from them (part 0 alone holds ≥ 16 ≥ top_k experts), ≤ 1024 list entries per part
+bool w4_gemm_moe_expert_major_pair_takes_lists(const MoeRouteLists& l, int num_experts, int num_valid_pairs, int top_k) {
+    if (!l.cand || !l.stats || !l.pub_expert_ids || !l.pub_expert_w) return false;
+    if ((l.Q != 2 && l.Q != 4) || top_k < 1 || top_k > 8) return false;
+    const int EQ = moe_route_part_experts(num_experts, l.Q);
+    if (EQ <= 0 || (long)(l.Q - 1) * EQ >= num_experts) return false;          // (every part has an expert)
+    return l.T >= 1 && l.T <= 128 && num_valid_pairs == l.T * top_k;
+}
+
 int w4_gemm_moe_expert_major_pair(const W4Device& gu, const W4Device& dn, const __half* x, __half* h, __half* out,
                                   const int32_t* pair_expert_ids, int num_experts, int num_valid_pairs, int top_k,
-                                  unsigned* arrive, unsigned* arrive_next, unsigned* timeout, int* took, hipStream_t stream) {
+                                  unsigned* arrive, unsigned* arrive_next, unsigned* timeout, int* took, hipStream_t stream,
+                                  const MoeRouteLists* lists) {
     *took = 0;
     if (num_valid_pairs <= 0) return 0;
     const bool zp = gu.zp != nullptr;
     if (!w4_gemm_moe_expert_major_pair_supports(gu, dn, num_experts, num_valid_pairs) || !arrive || !arrive_next || !timeout ||
-        !pair_expert_ids)
+        (!pair_expert_ids && !lists))
         return 0;
+    if (lists && !w4_gemm_moe_expert_major_pair_takes_lists(*lists, num_experts, num_valid_pairs, top_k)) return 0;
     W4Em2Args a{};
     a.gu_qw = gu.qw; a.gu_sc = gu.sc; a.gu_zp = gu.zp; a.gu_G = gu.G; a.gu_n64 = gu.n64;
     a.gu_stride_qw = (long)gu.n64 * gu.G * 4 * 64 * 4; a.gu_stride_sc = (long)gu.n64 * gu.G * 16 * 4;
@@ -2380,7 +2456,13 @@ int w4_gemm_moe_expert_major_pair(const W4Device& gu, const W4Device& dn, const 
 #endif
     const dim3 grid((unsigned)((gu.n64 + dn.n64) * num_experts), 1, 1);
     form_hit(FORM_MOE_EXPERT_MAJOR_PAIR);
-    if (zp) hipLaunchKernelGGL((w4_gemm_moe_em2_kernel<true>), grid, dim3(64), 0, stream, a);
+    if (lists) {
+        a.cand = lists->cand; a.stats = lists->stats; a.route_Q = lists->Q; a.route_EQ = moe_route_part_experts(num_experts, lists->Q); a.norm_topk = lists->norm_topk;
+        a.pub_ids = lists->pub_expert_ids; a.pub_w = lists->pub_expert_w;
+        form_hit(FORM_MOE_PAIR_RANK_LISTS);
+        if (zp) hipLaunchKernelGGL((w4_gemm_moe_em2_kernel<true, true>), grid, dim3(64), 0, stream, a);
+        else hipLaunchKernelGGL((w4_gemm_moe_em2_kernel<false, true>), grid, dim3(64), 0, stream, a);
+    } else if (zp) hipLaunchKernelGGL((w4_gemm_moe_em2_kernel<true>), grid, dim3(64), 0, stream, a);
     else hipLaunchKernelGGL((w4_gemm_moe_em2_kernel<false>), grid, dim3(64), 0, stream, a);
     FH_CHECK_LAUNCH();
     *took = 1;

@@ -395,6 +395,13 @@ class HipModel:
         _check(self.lib.ferrum_hip_model_read_taps(self.h, out.ctypes.data_as(C.POINTER(C.c_float)), tokens), "read_taps")
         return out
 
+    def read_routing(self, pairs):
+        """Expert ids and combine weights of the last MoE layer of the last forward, [pairs] each."""
+        ids, w = np.zeros(pairs, np.int32), np.zeros(pairs, np.float32)
+        _check(self.lib.ferrum_hip_model_read_routing(self.h, ids.ctypes.data_as(C.POINTER(C.c_int32)),
+                                                      w.ctypes.data_as(C.POINTER(C.c_float)), pairs), "read_routing")
+        return ids, w
+
     def time_kernel(self, which, n_seqs, max_kv_len, reps=3):
         """Mean µs per launch of a hot kernel (HIP events on the model stream) and the MoE block count."""
         names = {"moe_gate_up": 0, "moe_down": 1, "attention": 2, "qkv": 3, "o": 4, "lm_head": 5, "gate_up": 6, "down": 7, "moe_pair": 8}

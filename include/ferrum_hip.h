@@ -575,6 +575,9 @@ int ferrum_hip_model_decode_steps(FerrumHipModel* model, const uint64_t* seq_ids
 /* Tap for parity tests: hidden state after each layer of the LAST forward, fp32 [layers, T, H]. */
 int ferrum_hip_model_enable_taps(FerrumHipModel* model, int enable);
 int ferrum_hip_model_read_taps(FerrumHipModel* model, float* out_host, int max_tokens);
+/* Tap for routing tests: the expert id and the combine weight of every (token, slot) pair as the LAST MoE layer of the last
+ * forward left them, [pairs] each (pairs = tokens · top_k). */
+int ferrum_hip_model_read_routing(FerrumHipModel* model, int32_t* ids_host, float* weights_host, int pairs);
 int ferrum_hip_model_stream(FerrumHipModel* model, void** stream);
 /* Bench instrumentation: mean device time (µs, HIP events on the model stream) of one launch of a hot
  * kernel, cycled over every layer's weights with the index/routing state of the last forward.
