@@ -1054,8 +1054,18 @@ struct StepShape {
     int rest_min_q;          // … and the fewest tokens any item after them brings (0 when there is none)
 };
 
-template <typename T>
-T* idx(FerrumHipModel* m, size_t off) { return reinterpret_cast<T*>(m->idx_dev + off); }
+// The index block (layout m->il) as typed pointers: over the pinned host copy the callers fill, or over the device copy the kernels read
+struct IndexBlock { uint32_t *tokens, *cu, *pos, *kvl; int32_t *sampled_idx, *bt; };
+IndexBlock index_block(const FerrumHipModel* m, uint8_t* b) {
+    return {(uint32_t*)(b + m->il.tokens), (uint32_t*)(b + m->il.cu_seqlens), (uint32_t*)(b + m->il.pos_offsets),
+            (uint32_t*)(b + m->il.kv_lens), (int32_t*)(b + m->il.sampled_idx), (int32_t*)(b + m->il.block_tables)};
+}
+// one sequence's row of the host block table, padded with 0 (paged_pool.rs:438-440)
+void fill_block_table_row(const FerrumHipModel* m, int32_t* row, const SeqState& st) {
+    for (int b = 0; b < m->max_blocks_per_seq; b++) row[b] = b < (int)st.blocks.size() ? (int32_t)st.blocks[b] : 0;
+}
+
+#define FH_TRY(call) do { if (int rc_ = (call)) return rc_; } while (0)
 
 // Dense projection of the runner: act-order (desc_act) weights were repacked with their rows sorted by group, so the
 // input columns are gathered with the same permutation first (like the op-level ferrum_hip_gptq_linear_forward_f16).
@@ -1064,6 +1074,15 @@ T* idx(FerrumHipModel* m, size_t off) { return reinterpret_cast<T*>(m->idx_dev +
 // Under expert parallelism the kernels see the rank's own experts only: local ids (−1 = another rank's expert, ignored by
 // every form) and the local expert count.
 static const int32_t* moe_ids(const FerrumHipModel* m) { return m->cfg.expert_parallel ? m->expert_ids_local : m->expert_ids; }
+
+// Σ_e ceil(cnt_e/16) ≤ P/16 + min(P, E): the grid of 16-row blocks covers every block that can exist
+static int moe_max_blocks(int P, int E) { return std::min((P + E * 16) / 16, P / 16 + std::min(P, E)); }
+// the expert-major threshold compares pairs per expert: P pairs over num_experts, whatever share of them is local
+static bool moe_expert_major(const FerrumHipModel* m, int P) {
+    return m->moe_em_min_pairs_x8 > 0 && 8L * P >= (long)m->moe_em_min_pairs_x8 * m->cfg.num_experts;
+}
+// one half of the double-buffered arrival counters of the merged launches (layout: model_finalize)
+static unsigned* arrive_half(const FerrumHipModel* m, int parity) { return m->em2_arrive + (size_t)parity * m->arrive_half_words; }
 
 // Inputs of the two grouped GEMMs.  Act-order (desc_act) expert stacks read x'[j] = x[perm[j]] (the packed rows are in sorted-g_idx
 // order): the normalised rows / the gated activations are gathered by a launch in front of the GEMM (one per act-order stack and
@@ -1088,8 +1107,7 @@ static int moe_down_input(FerrumHipModel* m, LayerWeights& L, int P, hipStream_t
 // `route` (decode chain with a deferred merge): the routing arrives as per-part candidate lists; only forms that merge them in
 // their own prologue may run (moe_deferred_merge_ok decides that BEFORE the chain launch).
 static bool moe_pair_form(const FerrumHipModel* m, const LayerWeights& L, int P) {
-    return m->moe_em_min_pairs_x8 > 0 && 8L * P >= (long)m->moe_em_min_pairs_x8 * m->cfg.num_experts && knobs().moe_em2 &&
-           m->em2_arrive && !m->em2_failed && !L.exp_down.perm;
+    return moe_expert_major(m, P) && knobs().moe_em2 && m->em2_arrive && !m->em2_failed && !L.exp_down.perm;
 }
 static bool moe_deferred_merge_ok(const FerrumHipModel* m, const LayerWeights& L, int T, int Q) {
     if (!knobs().moe_deferred_merge || m->cfg.expert_parallel || Q < 2 || Q > 4 || m->cfg.top_k > 8) return false;
@@ -1102,13 +1120,20 @@ static bool moe_deferred_merge_ok(const FerrumHipModel* m, const LayerWeights& L
     return P <= std::min(knobs().moe_kw_pairs, 64) && T <= 4 && !moe_pair_form(m, L, P);
 }
 
-// router parts per token in the chain's role B
+// router parts per token (the chain's role B, the split route kernel)
 static int chain_route_parts(const FerrumHipModel* m) {
     if (m->cfg.num_experts <= 0) return 1;
     int Q = m->route_parts;
     const int tiles = (m->cfg.num_experts + 15) / 16;
     while (Q > 1 && (tiles % Q != 0 || Q > 8)) Q >>= 1;
     return Q;
+}
+// the router's candidate lists of T tokens in Q parts, as the runner's buffers hold them
+static MoeRouteLists route_lists(const FerrumHipModel* m, int T, int Q) {
+    MoeRouteLists l;
+    l.cand = m->route_cand; l.stats = m->route_stats; l.T = T; l.Q = Q; l.norm_topk = m->cfg.norm_topk_prob;
+    l.pub_expert_ids = m->expert_ids; l.pub_expert_w = m->expert_w;
+    return l;
 }
 // The expert pair resolves its rows from the lists itself (w4_gemm_moe_em2_kernel<…, LISTS>): wherever the pair is the batch's
 // form, the lists have the geometry its lookup takes and the list buffers hold them.  Decided BEFORE the chain launch, like
@@ -1117,10 +1142,8 @@ static bool moe_pair_rank_lists_ok(const FerrumHipModel* m, const LayerWeights& 
     if (!knobs().moe_pair_rank_lists || m->cfg.expert_parallel || !m->route_cand || !m->route_stats) return false;
     if ((long)T * Q > MOE_ROUTE_LIST_CAPACITY) return false;
     const int P = T * m->cfg.top_k;
-    MoeRouteLists l;
-    l.cand = m->route_cand; l.stats = m->route_stats; l.T = T; l.Q = Q; l.pub_expert_ids = m->expert_ids; l.pub_expert_w = m->expert_w;
     return moe_pair_form(m, L, P) && w4_gemm_moe_expert_major_pair_supports(L.exp_gate_up, L.exp_down, m->ep_E, P) &&
-           w4_gemm_moe_expert_major_pair_takes_lists(l, m->ep_E, P, m->cfg.top_k);
+           w4_gemm_moe_expert_major_pair_takes_lists(route_lists(m, T, Q), m->ep_E, P, m->cfg.top_k);
 }
 
 static int moe_decode_gemms(FerrumHipModel* m, LayerWeights& L, int P, int max_blocks, hipStream_t s, const MoeRouteLists* route = nullptr) {
@@ -1129,15 +1152,12 @@ static int moe_decode_gemms(FerrumHipModel* m, LayerWeights& L, int P, int max_b
     const int32_t* ids = moe_ids(m);
     const __half *gx = nullptr, *hx = nullptr;
     if (int rc = moe_gate_up_input(m, L, P / K, s, &gx)) return rc;
-    // (the expert-major threshold compares pairs per expert: P pairs over num_experts, whatever share of them is local)
-    if (m->moe_em_min_pairs_x8 > 0 && 8L * P >= (long)m->moe_em_min_pairs_x8 * c.num_experts) {
+    if (moe_expert_major(m, P)) {
         if (moe_pair_form(m, L, P)) {
             // one launch: down tiles wait for their expert's gate_up tiles inside it (w4_gemm_moe_em2_kernel)
-            unsigned* cur = m->em2_arrive + (size_t)m->em2_parity * m->arrive_half_words;
-            unsigned* nxt = m->em2_arrive + (size_t)(m->em2_parity ^ 1) * m->arrive_half_words;
             int took = 0;
-            if (int rc = w4_gemm_moe_expert_major_pair(L.exp_gate_up, L.exp_down, gx, m->moe_act, m->moe_down, ids, E, P, K, cur, nxt,
-                                                       m->inlaunch_timeouts, &took, s, route)) return rc;
+            if (int rc = w4_gemm_moe_expert_major_pair(L.exp_gate_up, L.exp_down, gx, m->moe_act, m->moe_down, ids, E, P, K, arrive_half(m, m->em2_parity),
+                                                       arrive_half(m, m->em2_parity ^ 1), m->inlaunch_timeouts, &took, s, route)) return rc;
             if (took) { m->em2_parity ^= 1; return 0; }
         }
         FH_REQUIRE(!route, "MoE decode: the routing was left as candidate lists but the batch takes the expert-major form");
@@ -1163,7 +1183,6 @@ static int moe_decode_gemms(FerrumHipModel* m, LayerWeights& L, int P, int max_b
 
 // gate_up (+silu·mul) and down grouped GEMMs for any batch size, straight from expert_ids: decode-sized batches (≤ 1024
 // pairs) without a separate align launch, else align + the block shape that fits the pairs per expert.
-#define FH_TRY(call) do { if (int rc_ = (call)) return rc_; } while (0)
 static int moe_batch_gemms(FerrumHipModel* m, LayerWeights& L, int P, int sorted_max, int max_blocks, hipStream_t s) {
     const FerrumHipModelConfig& c = m->cfg;
     const int E = m->ep_E, K = c.top_k, Eg = c.num_experts;     // block shapes are chosen by pairs per expert over ALL experts
@@ -1191,19 +1210,16 @@ static int moe_batch_gemms(FerrumHipModel* m, LayerWeights& L, int P, int sorted
     }
     if (bs == 16) {
         FH_TRY(moe_align_block_size(ids, m->sorted_ids, m->block_ids, m->total_post_pad, P, E, 16, sorted_max, s));
-        FH_TRY(w4_gemm_moe(L.exp_gate_up, gx, m->moe_act, m->sorted_ids, m->block_ids, m->total_post_pad, P,
-                        max_blocks, K, 1, s));
+        FH_TRY(w4_gemm_moe(L.exp_gate_up, gx, m->moe_act, m->sorted_ids, m->block_ids, m->total_post_pad, P, max_blocks, K, 1, s));
         FH_TRY(moe_down_input(m, L, P, s, &hx));
         return w4_gemm_moe(L.exp_down, hx, m->moe_down, m->sorted_ids, m->block_ids, m->total_post_pad, P, max_blocks, 1, 0, s);
     }
     const int sorted_max_bs = P + E * bs, max_blocks_bs = std::min(sorted_max_bs / bs, P / bs + std::min(P, E));
     FH_TRY(moe_align_block_size(ids, m->sorted_ids, m->block_ids, m->total_post_pad, P, E, bs, sorted_max_bs, s));
-    FH_TRY(w4_gemm_moe_tile(L.exp_gate_up, gx, m->moe_act, m->sorted_ids, m->block_ids, m->total_post_pad, P,
-                         max_blocks_bs, bs, K, 1, s));
+    FH_TRY(w4_gemm_moe_tile(L.exp_gate_up, gx, m->moe_act, m->sorted_ids, m->block_ids, m->total_post_pad, P, max_blocks_bs, bs, K, 1, s));
     FH_TRY(moe_down_input(m, L, P, s, &hx));
     return w4_gemm_moe_tile(L.exp_down, hx, m->moe_down, m->sorted_ids, m->block_ids, m->total_post_pad, P, max_blocks_bs, bs, 1, 0, s);
 }
-#undef FH_TRY
 
 int dense_linear(FerrumHipModel* m, const W4Device& w, const __half* x, __half* out, int T, hipStream_t s, bool x_permuted = false) {
     if (w.perm && (x_permuted || w.perm_folded)) form_hit(FORM_PERM_PRODUCER);
@@ -1215,67 +1231,106 @@ int dense_linear(FerrumHipModel* m, const W4Device& w, const __half* x, __half* 
     return w4_gemm_dense(w, x, out, T, m->workspace, m->workspace_bytes, s);
 }
 
-// Enqueue every kernel of one forward on m->stream.  Index tensors are already on the device.
 struct GreedyDeviceOpts {          // device pointers, already uploaded on m->stream
     const uint8_t* mask = nullptr; int mask_len = 0;
     const uint32_t* row_offsets = nullptr; const uint32_t* token_ids = nullptr; const float* penalties = nullptr;
 };
-int enqueue_forward(FerrumHipModel* m, const StepShape& sh, bool greedy, const GreedyDeviceOpts* gopts = nullptr,
-                    const DecodeAdvance* advance = nullptr, int* advance_fused = nullptr) {
-    if (advance_fused) *advance_fused = 0;
-    const FerrumHipModelConfig& c = m->cfg;
-    hipStream_t s = m->stream;
-    const int T = sh.m_total, H = c.hidden, nq = c.num_heads, nkv = c.num_kv_heads, hd = c.head_dim;
-    const int qk_mode = c.has_qk_norm ? 1 : 2;
-    const uint32_t* tokens = idx<uint32_t>(m, m->il.tokens);
-    const uint32_t* cu = idx<uint32_t>(m, m->il.cu_seqlens);
-    const uint32_t* pos = idx<uint32_t>(m, m->il.pos_offsets);
-    const uint32_t* kvl = idx<uint32_t>(m, m->il.kv_lens);
-    const int32_t* sampled_idx = idx<int32_t>(m, m->il.sampled_idx);
-    const int32_t* bt = idx<int32_t>(m, m->il.block_tables);
-    int rc;
-    // FERRUM_HIP_TRACE_LAUNCHES=1 (with FERRUM_HIP_NO_GRAPH=1: a stream cannot be synchronised inside a capture): every step of
-    // the forward is named on stderr and waited for, so a faulting kernel is the last line printed
-    const bool trace = knobs().trace_launches;
+
+// per-layer attention schedule (llama_layer_attention_schedule, llama_family.rs:1028-1045)
+struct AttnSchedule { int window; const float *cos_t, *sin_t; };
+static AttnSchedule attn_schedule(const FerrumHipModel* m, int li) {
+    const int pattern = m->cfg.sliding_window_pattern;
+    const bool is_global = pattern == 0 || (li + 1) % pattern == 0;
+    return {pattern == 0 ? m->cfg.sliding_window : (is_global ? 0 : m->cfg.sliding_window),
+            (!is_global && m->cos_local) ? m->cos_local : m->cos_t, (!is_global && m->sin_local) ? m->sin_local : m->sin_t};
+}
+// QK-norm weight argument of the attention kernels: models without QK-norm hand over a valid pointer that is never read
+static const __half* norm_w_or_input_ln(const LayerWeights& L, const __half* w) { return w ? w : L.input_ln; }
+
+// fp32 split-K slabs [S][rows_pad][n_pad] of a dense projection in the workspace: summed by the kernel that consumes them
+struct Slabs {
+    const float* base = nullptr; int S = 0, rows_pad = 0, n_pad = 0;
+    long stride() const { return (long)rows_pad * n_pad; }
+};
+
+// what plan_chain decides for a layer: whether one of the one-launch attention halves (chain.hip) is its form, and the launch
+enum ChainKind { CHAIN_NONE, CHAIN_DENSE, CHAIN_MOE };
+struct ChainPlan { ChainKind kind = CHAIN_NONE; DecodeChainDesc d; };
+
+// FERRUM_HIP_TRACE_LAUNCHES=1 (with FERRUM_HIP_NO_GRAPH=1: a stream cannot be synchronised inside a capture): every step of
+// the forward is named on stderr and waited for, so a faulting kernel is the last line printed
 #define RUN(x)                                                                       \
     do {                                                                             \
         if (trace) fprintf(stderr, "[ferrum_hip] T=%d %.70s\n", T, #x);              \
-        if ((rc = (x))) return rc;                                                   \
+        FH_TRY(x);                                                                   \
         if (trace) FH_CHECK_HIP(hipStreamSynchronize(s));                            \
     } while (0)
-    // arrival counters of the split route kernel: re-armed by the kernel itself, but zeroed per forward as well (by the head
-    // kernel below) so that an aborted launch can never poison the next one
-    const bool sandwich = c.sandwich_norms != 0;
+
+// One forward, enqueued on m->stream (the index tensors are already on the device): the stages that enqueue_forward below drives,
+// and what one layer hands to the next — a tail left for the next layer's first launch, the order its rows were written in.
+struct ForwardPass {
+    FerrumHipModel* const m; const StepShape& sh; const FerrumHipModelConfig& c; const hipStream_t s;
+    const int T, H, nq, nkv, hd, qk_mode;
+    const bool sandwich, trace;
+    const IndexBlock ix;                 // device index block
+    // ── carried from layer to layer ──
+    bool qkv_in_perm = false;            // norm_out holds the row in the next q|k|v's packed order
+    // decode at ≤ 4 rows (MoE models): the tail of layer l — combine + residual add + next input norm — runs as the prologue of
+    // layer l+1's q|k|v GEMM instead of as a launch of its own (every dependent launch costs ≈ 4 µs there)
+    bool pending_tail = false;
+    FusedCombineNorm tail{};
+    bool pending_chain_tail = false;     // MoE chain: combine + add + next input norm is the first role of the next layer's launch
+    bool pending_dense_tail = false;     // dense chain: MLP output (its down slabs, or mlp_out) + residual + next input norm likewise
+    Slabs dense_tail_slabs;
+    // ── the layer in flight ──
+    int li = 0; LayerWeights* Lp = nullptr;
+    const __half* next_ln = nullptr;            // the next layer's input norm (null behind the last layer) …
+    const int32_t* next_qkv_perm = nullptr;     // … and the act-order permutation of its q|k|v, if any
+
+    ForwardPass(FerrumHipModel* m_, const StepShape& sh_)
+        : m(m_), sh(sh_), c(m_->cfg), s(m_->stream), T(sh_.m_total), H(c.hidden), nq(c.num_heads), nkv(c.num_kv_heads), hd(c.head_dim),
+          qk_mode(c.has_qk_norm ? 1 : 2), sandwich(c.sandwich_norms != 0), trace(knobs().trace_launches), ix(index_block(m_, m_->idx_dev)) {
+        dense_tail_slabs.base = m->workspace;
+    }
+    void begin_layer(int l) {
+        li = l; Lp = &m->layers[l];
+        const bool last = l + 1 >= c.num_layers;
+        next_ln = last ? nullptr : m->layers[l + 1].input_ln;
+        next_qkv_perm = last ? nullptr : m->layers[l + 1].qkv.perm;
+    }
+    // (an act-order q|k|v of the next layer gets its rows permuted by the kernel that writes the next input norm)
+    bool next_in_perm() const { return next_ln && next_qkv_perm != nullptr; }
+
     // head, one launch: embedding_lookup (+ the Gemma embedding scale, llama_family.rs:3656) → residual stream (fp16; for
     // sandwich-norm models also the fp32 shadow, llama_family.rs:3664-3674) → layer 0's input norm.  Later layers get their
     // input norm fused into the previous layer's tail.
     // act-order (desc_act) projections read x'[j] = x[perm[j]]: the kernel that PRODUCES the row writes it permuted wherever one
     // workgroup owns the row (every norm of the dense layer) or the rows are few (decode attention scatters); the gated
     // activation is permuted by gate_up's column order (pack_gate_up).  Only the prefill o_proj keeps a gather launch.
-    RUN(embed_rms_norm_f16(m->embed, tokens, c.embed_scale, m->residual, sandwich ? m->residual_f32 : nullptr, m->layers[0].input_ln,
-                           c.rms_eps, m->norm_out, T, H, m->route_arrive, m->route_arrive ? 64 + (int)m->arrive_half_words : 0, s, m->layers[0].qkv.perm));
-    m->em2_parity = 0;          // the head kernel zeroed half 0 of the merged launches' counters; every such launch zeroes the other half
-    m->chain_parity = 0;
-    bool qkv_in_perm = m->layers[0].qkv.perm != nullptr;      // norm_out holds the row in L.qkv's packed order
-    // decode at ≤ 4 rows (MoE models): the tail of layer l — combine + residual add + next input norm — runs as the prologue of
-    // layer l+1's q|k|v GEMM instead of as a launch of its own (every dependent launch costs ≈ 4 µs there)
-    bool pending_tail = false;
-    FusedCombineNorm tail{};
-    bool pending_chain_tail = false;
-    auto chain_desc = [&](int li) {
-        LayerWeights& L = m->layers[li];
+    // The arrival counters of the split route kernel are re-armed by the kernel itself, but zeroed per forward as well (here) so
+    // that an aborted launch can never poison the next one.
+    int head() {
+        const LayerWeights& L0 = m->layers[0];
+        RUN(embed_rms_norm_f16(m->embed, ix.tokens, c.embed_scale, m->residual, sandwich ? m->residual_f32 : nullptr, L0.input_ln,
+                               c.rms_eps, m->norm_out, T, H, m->route_arrive, m->route_arrive ? 64 + (int)m->arrive_half_words : 0, s, L0.qkv.perm));
+        m->em2_parity = 0;          // the head kernel zeroed half 0 of the merged launches' counters; every such launch zeroes the other half
+        m->chain_parity = 0;
+        qkv_in_perm = L0.qkv.perm != nullptr;
+        return 0;
+    }
+
+    // ── the one-launch attention half of a decode layer (chain.hip) ──
+    DecodeChainDesc chain_desc(int l) const {
+        LayerWeights& L = m->layers[l];
         DecodeChainDesc d;
         d.T = T; d.H = H; d.nq = nq; d.nkv = nkv; d.head_dim = hd;
         d.top_k = c.top_k; d.down = m->moe_down; d.comb_w = m->expert_w; d.res_in = m->residual2; d.ln_in = L.input_ln; d.eps = c.rms_eps;
         d.res_a = m->residual; d.norm1 = m->norm_out;
         d.qkv = &L.qkv; d.qkv_out = m->qkv_out;
-        d.k_pool = L.k_pool; d.v_pool = L.v_pool; d.block_tables = bt; d.kv_lens = kvl;
-        d.q_norm_w = L.q_norm ? L.q_norm : L.input_ln; d.k_norm_w = L.k_norm ? L.k_norm : L.input_ln;
-        const int pattern = c.sliding_window_pattern;
-        const bool is_global = pattern == 0 || (li + 1) % pattern == 0;
-        d.sliding_window = pattern == 0 ? c.sliding_window : (is_global ? 0 : c.sliding_window);
-        d.cos_t = (!is_global && m->cos_local) ? m->cos_local : m->cos_t;
-        d.sin_t = (!is_global && m->sin_local) ? m->sin_local : m->sin_t;
+        d.k_pool = L.k_pool; d.v_pool = L.v_pool; d.block_tables = ix.bt; d.kv_lens = ix.kvl;
+        d.q_norm_w = norm_w_or_input_ln(L, L.q_norm); d.k_norm_w = norm_w_or_input_ln(L, L.k_norm);
+        const AttnSchedule as = attn_schedule(m, l);
+        d.sliding_window = as.window; d.cos_t = as.cos_t; d.sin_t = as.sin_t;
         d.qk_mode = qk_mode; d.max_blocks = m->max_blocks_per_seq;
         d.attn_out = m->attn_out; d.o = &L.o; d.o_out = m->o_out; d.o_part = m->chain_o_part;
         d.res_b_out = m->residual2; d.post_ln = L.post_ln; d.norm2 = m->norm_out; d.router_w = L.router;
@@ -1287,7 +1342,7 @@ int enqueue_forward(FerrumHipModel* m, const StepShape& sh, bool greedy, const G
         // W workgroups — W = 32 … 256 growing with the (sequence, kv head) count: the chain holds one workgroup per CU, and ranges
         // beyond that push the o_proj / router roles (which prefetch their weights while they wait) out of residence — but never
         // more than ≈ 1024 keys per range while 256 workgroups allow (profiles/r03_chain_kv_splits.txt: c × context × ranges)
-        const long keys = d.sliding_window > 0 ? std::min<long>(sh.max_kv_len, d.sliding_window) : sh.max_kv_len;
+        const long keys = chain_keys(d);
         const long units = (long)T * nkv, sk = std::max(1, knobs().chain_split_keys);
         const long cap_w = std::min<long>(256, std::max<long>(4 * units, std::min<long>(8 * units, 64)));
         long ns_l = std::min<long>({16, std::max<long>(1, cap_w / units), (keys + sk - 1) / sk});
@@ -1298,124 +1353,103 @@ int enqueue_forward(FerrumHipModel* m, const StepShape& sh, bool greedy, const G
         if (!m->chain_attn_partial || units > 4096 || knobs().chain_split_keys <= 0) ns = 1;
         d.attn_splits = ns; d.attn_partial = m->chain_attn_partial; d.attn_tickets = m->chain_attn_tickets;
         return d;
-    };
+    }
+    // the most keys one sequence's attention streams in this layer
+    long chain_keys(const DecodeChainDesc& d) const {
+        return d.sliding_window > 0 ? std::min<long>(sh.max_kv_len, d.sliding_window) : sh.max_kv_len;
+    }
     // The chain stays the layer's form while one attention workgroup has ≤ chain_max_keys (4096) keys to stream (more where T·nkv
     // workgroups already cover the chip twice); with its KV ranges it beat the stand-alone split-KV launches at every point measured
     // (c=1 at 32 k keys: 3.06 vs 3.52 ms per step; c=4 at 16 k: 3.62 vs 3.96; c=32 at 8 k: 7.85 vs 8.24) — beyond that is unmeasured
-    auto chain_kv_ok = [&](int li) {
-        const int pattern = c.sliding_window_pattern;
-        const bool is_global = pattern == 0 || (li + 1) % pattern == 0;
-        const int window = pattern == 0 ? c.sliding_window : (is_global ? 0 : c.sliding_window);
-        const long keys = window > 0 ? std::min<long>(sh.max_kv_len, window) : sh.max_kv_len;
-        return keys <= (long)knobs().chain_max_keys * chain_desc(li).attn_splits * std::max<long>(1, (long)T * nkv / 128);
-    };
-    auto chain_ok = [&](int li) {
+    bool chain_kv_ok(const DecodeChainDesc& d) const {
+        return chain_keys(d) <= (long)knobs().chain_max_keys * d.attn_splits * std::max<long>(1, (long)T * nkv / 128);
+    }
+    // MoE decode at ≤ 32 rows: [the previous layer's tail] + q|k|v + attention + o_proj + add/norm/route as ONE launch
+    // (chain.hip), then the merged gate_up → down launch: two launches per layer instead of seven
+    bool moe_chain_ok(const DecodeChainDesc& d) const {
         if (c.num_experts <= 0 || !knobs().decode_chain || m->em2_failed || !m->em2_arrive || !m->inlaunch_timeouts) return false;
         if (!sh.all_single_token || !m->fuse_rope_attn || T > knobs().chain_max_rows || m->taps_enabled || sandwich) return false;
         if (c.tp_world > 1 && c.expert_parallel != 2) return false;             // (tensor-parallel attention: an all-reduce sits behind o_proj)
-        if (T * c.top_k > 1024 || c.top_k > 8 || T > 128 || !chain_kv_ok(li)) return false;
-        return decode_chain_supports(chain_desc(li));
-    };
+        if (T * c.top_k > 1024 || c.top_k > 8 || T > 128 || !chain_kv_ok(d)) return false;
+        return decode_chain_supports(d);
+    }
     // dense models at 17–32 rows: the same launch for the attention half (tail of the previous layer's MLP — its down slabs +
     // residual + norm — q|k|v, attention, o_proj, add + norm), then gate_up slabs → gated activation → down slabs
-    bool pending_dense_tail = false;
-    int tail_S = 0, tail_rows_pad = 0, tail_n_pad = 0;
-    auto dense_chain_ok = [&](int li) {
-        const LayerWeights& L = m->layers[li];
+    bool dense_chain_ok(const LayerWeights& L, const DecodeChainDesc& d) const {
         if (c.num_experts > 0 || !knobs().decode_chain || !knobs().dense_chain || m->em2_failed || !m->em2_arrive || !m->inlaunch_timeouts || !m->residual2) return false;
         if (!sh.all_single_token || !m->fuse_rope_attn || T > std::min(64, knobs().chain_max_rows) || m->taps_enabled || sandwich || c.tp_world > 1) return false;      // (beyond 64 rows the 64-row GEMM tiles win: Llama-3.1-8B c=96 5.56 vs 5.61 ms)
         if (!L.o.qw || !L.gate_up.qw || !L.down.qw || L.gate_up.perm || L.down.perm || L.qkv.perm || L.o.perm) return false;
-        if (L.qkv.bias || L.o.bias || !chain_kv_ok(li)) return false;
-        DecodeChainDesc d = chain_desc(li);
-        d.has_a = false;
+        if (L.qkv.bias || L.o.bias || !chain_kv_ok(d)) return false;
         return decode_chain_supports(d);
-    };
-    for (int li = 0; li < c.num_layers; li++) {
-        LayerWeights& L = m->layers[li];
-        const __half* dummy = L.input_ln;
-        const __half* next_ln = li + 1 < c.num_layers ? m->layers[li + 1].input_ln : nullptr;
-        const int32_t* next_qkv_perm = li + 1 < c.num_layers ? m->layers[li + 1].qkv.perm : nullptr;
-        const int32_t* gu_perm = L.gate_up.perm;
-        // MoE decode at ≤ 32 rows: [the previous layer's tail] + q|k|v + attention + o_proj + add/norm/route as ONE launch
-        // (chain.hip), then the merged gate_up → down launch: two launches per layer instead of seven
-        if (dense_chain_ok(li)) {
-            DecodeChainDesc d = chain_desc(li);
-            d.has_a = pending_dense_tail;
-            d.a_slabs = m->workspace; d.a_S = tail_S; d.a_slab_stride = (long)tail_rows_pad * tail_n_pad; d.a_ld = tail_n_pad;
-            d.a_x = tail_S == 0 ? m->mlp_out : nullptr;
-            d.cnt = m->em2_arrive + (size_t)m->chain_parity * m->arrive_half_words;
-            d.cnt_next = m->em2_arrive + (size_t)(m->chain_parity ^ 1) * m->arrive_half_words;
-            RUN(decode_chain_f16(d, s));
-            m->chain_parity ^= 1;
-            pending_dense_tail = false;
-            form_hit(FORM_DENSE_CHAIN);
-            const int I = c.intermediate;
-            int S = 0, rows_pad = 0, n_pad = 0;
-            const bool slabs = m->dense_slabs && T > 16 && T <= 32;      // 17–32 rows: split-K slabs summed by their consumers
-            if (slabs) {
-                RUN(w4_gemm_dense_slabs_lds(L.gate_up, m->norm_out, m->workspace, m->workspace_bytes, T, &S, &rows_pad, &n_pad, s));
-                RUN(fused_gated_act_slabs_f16(m->workspace, S, (long)rows_pad * n_pad, n_pad, m->act_out, T, I, c.activation == 1, s));
-                S = 0;
-                RUN(w4_gemm_dense_slabs_lds(L.down, m->act_out, m->workspace, m->workspace_bytes, T, &S, &rows_pad, &n_pad, s));
-            } else {
-                RUN(dense_linear(m, L.gate_up, m->norm_out, m->gate_up_out, T, s, true));
-                if (c.activation == 1) { RUN(fused_gelu_tanh_mul_split_f16(m->gate_up_out, m->act_out, T, I, s)); }
-                else { RUN(fused_silu_mul_split_f16(m->gate_up_out, m->act_out, T, I, s)); }
-                RUN(dense_linear(m, L.down, m->act_out, m->mlp_out, T, s));
-            }
-            if (li + 1 < c.num_layers && dense_chain_ok(li + 1)) {
-                pending_dense_tail = true;          // MLP output + residual + next input norm: the first role of the next layer's launch
-                tail_S = S; tail_rows_pad = rows_pad; tail_n_pad = n_pad;
-            } else if (!slabs) {
-                if (next_ln) { RUN(fused_add_rms_norm_f16(m->residual2, m->mlp_out, next_ln, c.rms_eps, m->norm_out, T, H, s, next_qkv_perm)); }
-                else { RUN(add_inplace_f16(m->residual2, m->mlp_out, (long)T * H, s)); }
-                FH_CHECK_HIP(hipMemcpyAsync(m->residual, m->residual2, (size_t)T * H * sizeof(__half), hipMemcpyDeviceToDevice, s));
-                qkv_in_perm = next_ln && next_qkv_perm != nullptr;
-            } else {
-                // (the residual of this layer sits in the ping-pong buffer: the stand-alone tail works on it in place, then it moves back)
-                RUN(fused_add_rms_norm_route_slabs_f16(m->residual2, nullptr, m->workspace, S, (long)rows_pad * n_pad, n_pad,
-                                                       next_ln ? next_ln : L.input_ln, c.rms_eps, m->norm_out, nullptr, 0, 0, 0, nullptr, nullptr,
-                                                       nullptr, T, H, s, next_qkv_perm));
-                FH_CHECK_HIP(hipMemcpyAsync(m->residual, m->residual2, (size_t)T * H * sizeof(__half), hipMemcpyDeviceToDevice, s));
-                qkv_in_perm = next_ln && next_qkv_perm != nullptr;
-            }
-            continue;
+    }
+    // (the dense chain is tested first; the description leaves here without a tail role — the layer body adds it)
+    ChainPlan plan_chain(int l) const {
+        ChainPlan p;
+        p.d = chain_desc(l);
+        p.kind = dense_chain_ok(m->layers[l], p.d) ? CHAIN_DENSE : moe_chain_ok(p.d) ? CHAIN_MOE : CHAIN_NONE;
+        return p;
+    }
+
+    int dense_chain_layer(DecodeChainDesc d, bool next_chained) {
+        LayerWeights& L = *Lp;
+        const Slabs& a = dense_tail_slabs;
+        d.has_a = pending_dense_tail;
+        d.a_slabs = a.base; d.a_S = a.S; d.a_slab_stride = a.stride(); d.a_ld = a.n_pad;
+        d.a_x = a.S == 0 ? m->mlp_out : nullptr;
+        d.cnt = arrive_half(m, m->chain_parity);
+        d.cnt_next = arrive_half(m, m->chain_parity ^ 1);
+        RUN(decode_chain_f16(d, s));
+        m->chain_parity ^= 1;
+        pending_dense_tail = false;
+        form_hit(FORM_DENSE_CHAIN);
+        Slabs down{m->workspace};
+        const bool slabs = m->dense_slabs && T > 16 && T <= 32;      // 17–32 rows: split-K slabs summed by their consumers
+        if (slabs) {
+            RUN(gate_up_act(true));
+            RUN(w4_gemm_dense_slabs_lds(L.down, m->act_out, m->workspace, m->workspace_bytes, T, &down.S, &down.rows_pad, &down.n_pad, s));
+        } else {
+            RUN(dense_mlp_ops());
         }
-        if (chain_ok(li)) {
-            const int E = c.num_experts, K = c.top_k, P = T * K, sorted_max = P + E * 16;
-            const int max_blocks = std::min(sorted_max / 16, P / 16 + std::min(P, E));
-            DecodeChainDesc d = chain_desc(li);
-            d.has_a = pending_chain_tail;
-            d.cnt = m->em2_arrive + (size_t)m->chain_parity * m->arrive_half_words + (size_t)c.num_experts * MOE_PAIR_COUNTER_STRIDE;
-            d.cnt_next = m->em2_arrive + (size_t)(m->chain_parity ^ 1) * m->arrive_half_words + (size_t)c.num_experts * MOE_PAIR_COUNTER_STRIDE;
-            // the Q candidate lists of a token are merged by the grouped GEMM's prologue (under its first weight loads) where that
-            // form runs, instead of by role B's first part at the end of the chain (≈ 3.7 µs of every layer)
-            // … or, where the layer's grouped GEMMs are the expert pair, looked up by each of its tiles for its own expert
-            d.defer_merge = d.Q > 1 && (moe_deferred_merge_ok(m, L, T, d.Q) || moe_pair_rank_lists_ok(m, L, T, d.Q));
-            MoeRouteLists lists;
-            lists.cand = m->route_cand; lists.stats = m->route_stats; lists.T = T; lists.Q = d.Q; lists.norm_topk = c.norm_topk_prob;
-            lists.pub_expert_ids = m->expert_ids; lists.pub_expert_w = m->expert_w;
-            RUN(decode_chain_f16(d, s));
-            m->chain_parity ^= 1;
-            pending_chain_tail = false;
-            form_hit(d.Q > 1 ? FORM_ROUTE_SPLIT : FORM_ROUTE_FUSED);
-            if (c.expert_parallel) RUN(moe_remap_expert_ids(m->expert_ids, m->expert_ids_local, P, m->ep_e0, m->ep_E, s));
-            RUN(moe_decode_gemms(m, L, P, max_blocks, s, d.defer_merge ? &lists : nullptr));
-            if (!c.expert_parallel && li + 1 < c.num_layers && chain_ok(li + 1)) {
-                pending_chain_tail = true;          // combine + add + next input norm: the first role of the next layer's launch
-            } else if (!c.expert_parallel) {
-                RUN(moe_combine_add_rms_norm_f16(m->moe_down, m->expert_w, m->residual2, m->residual, next_ln, c.rms_eps, m->norm_out, T, K, H, s,
-                                                 next_qkv_perm));
-                qkv_in_perm = next_ln && next_qkv_perm != nullptr;
-            } else {
-                RUN(moe_combine_local_f16(m->moe_down, m->expert_w, m->expert_ids_local, m->mlp_out, T, K, H, s));
-                RUN(tp_all_reduce(m, m->mlp_out, (size_t)T * H));
-                RUN(moe_combine_add_rms_norm_f16(m->mlp_out, m->ones, m->residual2, m->residual, next_ln, c.rms_eps, m->norm_out, T, 1, H, s,
-                                                 next_qkv_perm));
-                qkv_in_perm = next_ln && next_qkv_perm != nullptr;
-            }
-            continue;
+        if (next_chained) {
+            pending_dense_tail = true;          // MLP output + residual + next input norm: the first role of the next layer's launch
+            dense_tail_slabs = down;
+            return 0;
         }
+        // (the residual of this layer sits in the ping-pong buffer: the stand-alone tail works on it in place, then it moves back)
+        if (slabs) RUN(slab_tail(down, m->residual2, L.post_ffn_ln, next_ln, next_qkv_perm));
+        else RUN(dense_tail(m->mlp_out, m->residual2, L.post_ffn_ln, next_ln, next_qkv_perm));
+        FH_CHECK_HIP(hipMemcpyAsync(m->residual, m->residual2, (size_t)T * H * sizeof(__half), hipMemcpyDeviceToDevice, s));
+        qkv_in_perm = next_in_perm();
+        return 0;
+    }
+
+    int moe_chain_layer(DecodeChainDesc d, bool next_chained) {
+        LayerWeights& L = *Lp;
+        const int P = T * c.top_k;
+        const size_t behind_pair = (size_t)c.num_experts * MOE_PAIR_COUNTER_STRIDE;      // the chain's counters follow the pair's in each half
+        d.has_a = pending_chain_tail;
+        d.cnt = arrive_half(m, m->chain_parity) + behind_pair;
+        d.cnt_next = arrive_half(m, m->chain_parity ^ 1) + behind_pair;
+        // the Q candidate lists of a token are merged by the grouped GEMM's prologue (under its first weight loads) where that
+        // form runs, instead of by role B's first part at the end of the chain (≈ 3.7 µs of every layer)
+        // … or, where the layer's grouped GEMMs are the expert pair, looked up by each of its tiles for its own expert
+        d.defer_merge = d.Q > 1 && (moe_deferred_merge_ok(m, L, T, d.Q) || moe_pair_rank_lists_ok(m, L, T, d.Q));
+        const MoeRouteLists lists = route_lists(m, T, d.Q);
+        RUN(decode_chain_f16(d, s));
+        m->chain_parity ^= 1;
+        pending_chain_tail = false;
+        form_hit(d.Q > 1 ? FORM_ROUTE_SPLIT : FORM_ROUTE_FUSED);
+        RUN(after_route(P));
+        RUN(moe_decode_gemms(m, L, P, moe_max_blocks(P, c.num_experts), s, d.defer_merge ? &lists : nullptr));
+        if (!c.expert_parallel && next_chained) pending_chain_tail = true;
+        else RUN(moe_tail(m->residual2, m->residual));
+        return 0;
+    }
+
+    // ── the multi-launch layer ──
+    // q|k|v GEMM, then QK-norm + RoPE + KV write + attention.  *attn_perm: attn_out holds the row in L.o's packed order
+    int qkv_attention(bool* attn_perm) {
+        LayerWeights& L = *Lp;
         if (pending_tail) {
             RUN(w4_gemm_dense(L.qkv, nullptr, m->qkv_out, T, m->workspace, m->workspace_bytes, s, &tail));
             pending_tail = false;
@@ -1423,304 +1457,329 @@ int enqueue_forward(FerrumHipModel* m, const StepShape& sh, bool greedy, const G
             RUN(dense_linear(m, L.qkv, m->norm_out, m->qkv_out, T, s, qkv_in_perm));
         }
         qkv_in_perm = false;
-        bool attn_perm = false;          // attn_out holds the row in L.o's packed order
-        // per-layer attention schedule (llama_layer_attention_schedule, llama_family.rs:1028-1045)
-        const int pattern = c.sliding_window_pattern;
-        const bool is_global = pattern == 0 || (li + 1) % pattern == 0;
-        const int layer_window = pattern == 0 ? c.sliding_window : (is_global ? 0 : c.sliding_window);
-        const float* cos_l = (!is_global && m->cos_local) ? m->cos_local : m->cos_t;
-        const float* sin_l = (!is_global && m->sin_local) ? m->sin_local : m->sin_t;
-        const bool layer_decode = sh.pure_decode && layer_window == 0;
+        *attn_perm = false;
+        const AttnSchedule as = attn_schedule(m, li);
+        const __half *q_norm = norm_w_or_input_ln(L, L.q_norm), *k_norm = norm_w_or_input_ln(L, L.k_norm);
+        const int mb = m->max_blocks_per_seq;
         if (sh.all_single_token && m->fuse_rope_attn && nq / nkv <= 14) {
             // decode: QK-norm + RoPE + KV write happen in the attention kernel's prologue (one launch fewer)
-            RUN(paged_decode_attention_fused_qkv_f16(m->qkv_out, L.q_norm ? L.q_norm : dummy, L.k_norm ? L.k_norm : dummy,
-                                                     cos_l, sin_l, c.rms_eps, qk_mode, L.k_pool, L.v_pool, m->attn_out,
-                                                     bt, kvl, sh.num_seqs, sh.max_kv_len, nq, nkv, hd, layer_window, KV_BLOCK,
-                                                     m->max_blocks_per_seq, m->workspace, m->workspace_bytes, s, L.o.inv_perm));
-            attn_perm = L.o.perm != nullptr;
+            RUN(paged_decode_attention_fused_qkv_f16(m->qkv_out, q_norm, k_norm, as.cos_t, as.sin_t, c.rms_eps, qk_mode, L.k_pool, L.v_pool,
+                                                     m->attn_out, ix.bt, ix.kvl, sh.num_seqs, sh.max_kv_len, nq, nkv, hd, as.window, KV_BLOCK,
+                                                     mb, m->workspace, m->workspace_bytes, s, L.o.inv_perm));
+            *attn_perm = L.o.perm != nullptr;
+            return 0;
+        }
+        RUN(split_qkv_norm_rope_into_paged_cache_varlen_f16(m->qkv_out, q_norm, k_norm, as.cos_t, as.sin_t, m->q_out, L.k_pool, L.v_pool,
+                                                            ix.cu, ix.pos, ix.bt, sh.num_seqs, T, nq, nkv, hd, c.rms_eps, qk_mode, KV_BLOCK, mb, s));
+        if (sh.pure_decode && as.window == 0) {
+            RUN(paged_batched_decode_attention_f16(m->q_out, L.k_pool, L.v_pool, m->attn_out, ix.bt, ix.kvl, sh.num_seqs, sh.max_kv_len, nq, nkv, hd,
+                                                   KV_BLOCK, mb, m->workspace, m->workspace_bytes, s, L.o.inv_perm));
+            *attn_perm = L.o.perm != nullptr;
+        } else if (sh.single_prefix > 0 && sh.single_prefix < sh.num_seqs && (long)sh.rest_min_q * (nq / nkv) >= 16L * m->attn_flash_min_rows) {
+            // decode rows first, LONG prompts after them (≥ 1024 tokens at a GQA group of 8; for a 256-token prompt the
+            // second launch costs more than the form saves: 9.7 → 10.2 ms per iteration): two launches, so that the
+            // prompts take the LDS-shared K/V form and the decode rows the KV-split form (q/out are indexed by the
+            // absolute token offsets in cu_seqlens_q, so sub-ranges of the sequence arrays are enough)
+            const int n1 = sh.single_prefix;
+            RUN(varlen_attention(as.window, 0, n1, n1, 1));
+            RUN(varlen_attention(as.window, n1, sh.num_seqs - n1, T - n1, sh.max_q_len));
         } else {
-            RUN(split_qkv_norm_rope_into_paged_cache_varlen_f16(m->qkv_out, L.q_norm ? L.q_norm : dummy,
-                                                                L.k_norm ? L.k_norm : dummy, cos_l, sin_l, m->q_out,
-                                                                L.k_pool, L.v_pool, cu, pos, bt, sh.num_seqs, T, nq, nkv, hd,
-                                                                c.rms_eps, qk_mode, KV_BLOCK, m->max_blocks_per_seq, s));
-            if (layer_decode) {
-                RUN(paged_batched_decode_attention_f16(m->q_out, L.k_pool, L.v_pool, m->attn_out, bt, kvl, sh.num_seqs,
-                                                       sh.max_kv_len, nq, nkv, hd, KV_BLOCK, m->max_blocks_per_seq,
-                                                       m->workspace, m->workspace_bytes, s, L.o.inv_perm));
-                attn_perm = L.o.perm != nullptr;
-            } else if (sh.single_prefix > 0 && sh.single_prefix < sh.num_seqs && (long)sh.rest_min_q * (nq / nkv) >= 16L * m->attn_flash_min_rows) {
-                // decode rows first, LONG prompts after them (≥ 1024 tokens at a GQA group of 8; for a 256-token prompt the
-                // second launch costs more than the form saves: 9.7 → 10.2 ms per iteration): two launches, so that the
-                // prompts take the LDS-shared K/V form and the decode rows the KV-split form (q/out are indexed by the
-                // absolute token offsets in cu_seqlens_q, so sub-ranges of the sequence arrays are enough)
-                const int n1 = sh.single_prefix;
-                RUN(paged_varlen_attention_f16(m->q_out, L.k_pool, L.v_pool, m->attn_out, cu, pos, bt, n1, n1, 1, sh.max_kv_len, nq,
-                                               nkv, hd, layer_window, KV_BLOCK, m->max_blocks_per_seq, m->workspace,
-                                               m->workspace_bytes, s));
-                RUN(paged_varlen_attention_f16(m->q_out, L.k_pool, L.v_pool, m->attn_out, cu + n1, pos + n1,
-                                               bt + (size_t)n1 * m->max_blocks_per_seq, sh.num_seqs - n1, T - n1, sh.max_q_len,
-                                               sh.max_kv_len, nq, nkv, hd, layer_window, KV_BLOCK, m->max_blocks_per_seq,
-                                               m->workspace, m->workspace_bytes, s));
-            } else {
-                RUN(paged_varlen_attention_f16(m->q_out, L.k_pool, L.v_pool, m->attn_out, cu, pos, bt, sh.num_seqs, T,
-                                               sh.max_q_len, sh.max_kv_len, nq, nkv, hd, layer_window, KV_BLOCK,
-                                               m->max_blocks_per_seq, m->workspace, m->workspace_bytes, s));
-            }
+            RUN(varlen_attention(as.window, 0, sh.num_seqs, T, sh.max_q_len));
         }
-        if (c.num_experts > 0) {
-            const int E = c.num_experts, K = c.top_k, P = T * K, sorted_max = P + E * 16;
-            // Σ_e ceil(cnt_e/16) ≤ P/16 + min(P, E): the grid covers every block that can exist
-            const int max_blocks = std::min(sorted_max / 16, P / 16 + std::min(P, E));
-            const int tiles = (E + 15) / 16;
-            int Q = m->route_parts;
-            while (Q > 1 && (tiles % Q != 0 || Q > 8)) Q >>= 1;
-            // attention heads sharded, o_proj row-parallel: all-reduce before the add + norm + route kernel (expert_parallel 2 keeps
-            // attention replicated: full heads on every rank, nothing to reduce there)
-            const bool tp = c.tp_world > 1 && c.expert_parallel != 2;
-            const bool ep = c.expert_parallel != 0;
-            // expert parallel: after routing, the pair ids become local ids (−1 = another rank's expert)
-            auto after_route = [&]() -> int {
-                return ep ? moe_remap_expert_ids(m->expert_ids, m->expert_ids_local, P, m->ep_e0, m->ep_E, s) : 0;
-            };
-            // the layer tail: residual_out = residual_in + Σ_k w_k·down_k, then the next input norm.  Expert parallel: the sum over
-            // the rank's own experts is a partial [T, H] that meets the other ranks' in the all-reduce a dense MLP uses, and the
-            // reduced row then enters the residual like a single expert row of weight 1 (the same kernel, top_k = 1)
-            auto moe_tail = [&](const __half* res_in, __half* res_out) -> int {
-                // (an act-order q|k|v of the next layer gets its rows permuted by this kernel)
-                qkv_in_perm = next_ln && next_qkv_perm != nullptr;
-                if (!ep)
-                    return moe_combine_add_rms_norm_f16(m->moe_down, m->expert_w, res_in, res_out, next_ln, c.rms_eps, m->norm_out, T, K, H, s, next_qkv_perm);
-                if (int rc_ = moe_combine_local_f16(m->moe_down, m->expert_w, m->expert_ids_local, m->mlp_out, T, K, H, s)) return rc_;
-                if (int rc_ = tp_all_reduce(m, m->mlp_out, (size_t)T * H)) return rc_;
-                return moe_combine_add_rms_norm_f16(m->mlp_out, m->ones, res_in, res_out, next_ln, c.rms_eps, m->norm_out, T, 1, H, s, next_qkv_perm);
-            };
-            const bool decode_fast = T <= 64 && P <= 1024 && K <= 8 && Q >= 1 && tiles / Q <= 8 && (!L.o.perm || attn_perm);
-            const bool o_quant = L.o.qw != nullptr;           // the slab forms are INT4 kernels; an unquantised o_proj takes the direct GEMM
-            if (decode_fast) {
-                // o_proj as fp32 split-K slabs, reduced inside the next kernel (no reduce launch)
-                const float* slabs = nullptr;
-                int S = m->o_slabs, rows_pad = 0, n_pad = 0;
-                if (tp || !o_quant) {
-                    RUN(dense_linear(m, L.o, m->attn_out, m->o_out, T, s, attn_perm));
-                    if (tp) RUN(tp_all_reduce(m, m->o_out, (size_t)T * H));
-                    S = 0;
-                } else if (S > 0 && T > 16 && T <= 32 && !L.o.bias) {
-                    if (L.o.perm) form_hit(FORM_PERM_PRODUCER);          // (attn_perm: the decode attention wrote the permuted rows)
-                    // 17–32 rows: activations staged once per workgroup in LDS (a wave fetching its own fragments pulls 2× the
-                    // weight bytes from L2); decode c=32 4.60 → 4.57 ms per step
-                    RUN(w4_gemm_dense_slabs_lds(L.o, m->attn_out, m->workspace, m->workspace_bytes, T, &S, &rows_pad, &n_pad, s));
-                    slabs = m->workspace;
-                } else if (S > 0) {
-                    if (L.o.perm) form_hit(FORM_PERM_PRODUCER);
-                    RUN(w4_gemm_dense_slabs(L.o, m->attn_out, m->workspace, m->workspace_bytes, T, S, &rows_pad, &n_pad, s));
-                    slabs = m->workspace;
-                    S = std::min(S, L.o.G);
-                } else {
-                    RUN(dense_linear(m, L.o, m->attn_out, m->o_out, T, s, attn_perm));
-                }
-                form_hit(Q > 1 ? FORM_ROUTE_SPLIT : FORM_ROUTE_FUSED);
-                if (Q > 1) {
-                    // B over Q expert parts per token (one CU pulls the 512-KB router at ≈70 GB/s; Q CUs share it):
-                    // residual → residual2 (ping-pong), norm_out; each token's last-arriving part merges the Q
-                    // candidate lists inside the launch and writes expert_ids / expert_w.
-                    RUN(fused_add_rms_norm_route_split_f16(m->residual, m->residual2, m->o_out, slabs, S, (long)rows_pad * n_pad,
-                                                           n_pad, L.post_ln, c.rms_eps, m->norm_out, L.router, E, K, Q,
-                                                           m->route_cand, m->route_stats, m->route_arrive, c.norm_topk_prob,
-                                                           m->expert_ids, m->expert_w, nullptr, T, H, s));
-                    RUN(after_route());
-                    RUN(moe_decode_gemms(m, L, P, max_blocks, s));
-                    if (T <= m->fuse_tail_max_rows && next_ln && !m->taps_enabled && !ep &&
-                        w4_gemm_dense_can_fuse_combine_norm(m->layers[li + 1].qkv, T)) {
-                        tail = FusedCombineNorm{m->moe_down, m->expert_w, m->residual2, m->residual, next_ln, c.rms_eps, K};
-                        pending_tail = true;
-                    } else {
-                        RUN(moe_tail(m->residual2, m->residual));
-                    }
-                } else {
-                    RUN(fused_add_rms_norm_route_slabs_f16(m->residual, m->o_out, slabs, S, (long)rows_pad * n_pad, n_pad, L.post_ln,
-                                                           c.rms_eps, m->norm_out, L.router, E, K, c.norm_topk_prob, m->expert_ids,
-                                                           m->expert_w, nullptr, T, H, s));
-                    RUN(after_route());
-                    RUN(moe_decode_gemms(m, L, P, max_blocks, s));
-                    RUN(moe_tail(m->residual, m->residual));
-                }
-            } else if (T >= 64 && T < m->route_gemm_min_tokens && !tp && o_quant && !L.o.perm && !L.o.bias && m->o_slabs > 0) {
-                // short prefill / a prompt riding along with the decode batch: o_proj as fp32 split-K slabs straight into the
-                // add + norm + route kernel (no reduce launch)
-                int S = 1, rows_pad = 0, n_pad = 0;
-                RUN(w4_gemm_dense_slabs_tile(L.o, m->attn_out, m->workspace, m->workspace_bytes, T, &S, &rows_pad, &n_pad, s));
-                RUN(fused_add_rms_norm_route_slabs_f16(m->residual, m->o_out, m->workspace, S, (long)rows_pad * n_pad, n_pad, L.post_ln,
-                                                       c.rms_eps, m->norm_out, L.router, E, K, c.norm_topk_prob, m->expert_ids,
-                                                       m->expert_w, nullptr, T, H, s));
-                RUN(after_route());
-                RUN(moe_batch_gemms(m, L, P, sorted_max, max_blocks, s));
-                RUN(moe_tail(m->residual, m->residual));
-            } else {
-                RUN(dense_linear(m, L.o, m->attn_out, m->o_out, T, s, attn_perm));
-                if (tp) RUN(tp_all_reduce(m, m->o_out, (size_t)T * H));
-                form_hit(T >= m->route_gemm_min_tokens ? FORM_ROUTE_GEMM : FORM_ROUTE_FUSED);
-                if (T >= m->route_gemm_min_tokens) {
-                    // prefill: one workgroup per token would pull the whole router (E·H·2 B) from L2 per token (2048 tokens:
-                    // 1 GB, 95 µs) — run the router as a GEMM over all tokens instead, then the top-k kernel
-                    RUN(fused_add_rms_norm_f16(m->residual, m->o_out, L.post_ln, c.rms_eps, m->norm_out, T, H, s));
-                    if (knobs().route_gemm_topk && !m->taps_enabled && moe_route_gemm_topk_supports(E, H, K)) {
-                        // … and the top-k in the same workgroups: the logits stay on the CU (8192 tokens: 27 + 7 + 16 µs → one launch)
-                        form_hit(FORM_ROUTE_GEMM_TOPK);
-                        RUN(moe_route_gemm_topk_f16(m->norm_out, L.router, m->expert_ids, m->expert_w, T, E, H, K, c.norm_topk_prob, s));
-                    } else {
-                        RUN(f16t_gemm_f32out(m->norm_out, L.router, m->router_logits, T, E, H, m->workspace, m->workspace_bytes, s));
-                        RUN(moe_route_topk_softmax_f32(m->router_logits, m->expert_ids, m->expert_w, T, E, K, c.norm_topk_prob, s));
-                    }
-                } else {
-                    // residual += o; post-attention norm; router logits; top-k — one launch (fused.hip B)
-                    RUN(fused_add_rms_norm_route_f16(m->residual, m->o_out, L.post_ln, c.rms_eps, m->norm_out, L.router, E, K,
-                                                     c.norm_topk_prob, m->expert_ids, m->expert_w, nullptr, T, H, s));
-                }
-                RUN(after_route());
-                RUN(moe_batch_gemms(m, L, P, sorted_max, max_blocks, s));
-                RUN(moe_tail(m->residual, m->residual));
-            }
-        } else {
-            const int I = c.intermediate;
-            // 17–32 rows, one GPU: every projection of the MLP block writes fp32 split-K slabs (LDS-shared activations) and
-            // the consumer that exists anyway — add+norm, gated activation — sums them: no reduce launches.
-            // Tensor parallel (o / down row-parallel): the partial sums of the ranks meet in an all-reduce, so those two
-            // projections produce fp16 partials (GEMM + reduce), all-reduce, then add + norm; the column-parallel gate_up keeps
-            // its slabs → gated-activation form.  Everything stays stream-ordered device work, so the step is still one graph.
-            const bool tp = c.tp_world > 1;
-            // (act-order projections: every input of the chain arrives permuted from its producer — decode attention, the norms
-            // below, gate_up's column order)
-            const bool slab_chain = m->dense_slabs && T > 16 && T <= 32 && (!L.o.perm || attn_perm) && (!L.down.perm || L.down.perm_folded) &&
-                                    L.o.qw && L.gate_up.qw && L.down.qw;   // INT4 slab kernels; unquantised projections take the op chain
-            int S = 0, rows_pad = 0, n_pad = 0;
-            if (slab_chain) {
-                form_hit(FORM_DENSE_SLAB_CHAIN);
-                if (tp) {
-                    RUN(dense_linear(m, L.o, m->attn_out, m->o_out, T, s, attn_perm));
-                    if (sandwich) {
-                        RUN(tp_all_reduce(m, m->o_out, (size_t)T * H));
-                        RUN(sandwich_add_rms_norm_f32(m->o_out, L.post_attn_ln, m->residual_f32, L.post_ln, c.rms_eps, m->norm_out, T, H, s, gu_perm));
-                    } else {
-                        RUN(tp_all_reduce_add_rms_norm(m, m->o_out, m->residual, L.post_ln, c.rms_eps, m->norm_out, T, H, s, gu_perm));
-                    }
-                } else {
-                if (L.o.perm) form_hit(FORM_PERM_PRODUCER);
-                RUN(w4_gemm_dense_slabs_lds(L.o, m->attn_out, m->workspace, m->workspace_bytes, T, &S, &rows_pad, &n_pad, s));
-                if (sandwich) {
-                    RUN(sandwich_add_rms_norm_f32_slabs(m->workspace, S, (long)rows_pad * n_pad, n_pad, L.post_attn_ln, m->residual_f32,
-                                                        L.post_ln, c.rms_eps, m->norm_out, T, H, s, gu_perm));
-                } else {
-                    RUN(fused_add_rms_norm_route_slabs_f16(m->residual, nullptr, m->workspace, S, (long)rows_pad * n_pad, n_pad, L.post_ln,
-                                                           c.rms_eps, m->norm_out, nullptr, 0, 0, 0, nullptr, nullptr, nullptr, T, H, s, gu_perm));
-                }
-                }
-                if (gu_perm) form_hit(FORM_PERM_PRODUCER);
-                if (L.down.perm) form_hit(FORM_PERM_PRODUCER);
-                S = 0;
-                RUN(w4_gemm_dense_slabs_lds(L.gate_up, m->norm_out, m->workspace, m->workspace_bytes, T, &S, &rows_pad, &n_pad, s));
-                RUN(fused_gated_act_slabs_f16(m->workspace, S, (long)rows_pad * n_pad, n_pad, m->act_out, T, I, c.activation == 1, s));
-                S = 0;
-                if (tp) {
-                    RUN(dense_linear(m, L.down, m->act_out, m->mlp_out, T, s));
-                    if (sandwich) {
-                        RUN(tp_all_reduce(m, m->mlp_out, (size_t)T * H));
-                        RUN(sandwich_add_rms_norm_f32(m->mlp_out, L.post_ffn_ln, m->residual_f32, next_ln, c.rms_eps, m->norm_out, T, H, s, next_qkv_perm));
-                    } else if (next_ln) {
-                        RUN(tp_all_reduce_add_rms_norm(m, m->mlp_out, m->residual, next_ln, c.rms_eps, m->norm_out, T, H, s, next_qkv_perm));
-                    } else {
-                        RUN(tp_all_reduce(m, m->mlp_out, (size_t)T * H));
-                        RUN(add_inplace_f16(m->residual, m->mlp_out, (long)T * H, s));
-                    }
-                } else {
-                RUN(w4_gemm_dense_slabs_lds(L.down, m->act_out, m->workspace, m->workspace_bytes, T, &S, &rows_pad, &n_pad, s));
-                if (sandwich) {
-                    RUN(sandwich_add_rms_norm_f32_slabs(m->workspace, S, (long)rows_pad * n_pad, n_pad, L.post_ffn_ln, m->residual_f32,
-                                                        next_ln, c.rms_eps, m->norm_out, T, H, s, next_qkv_perm));
-                } else {
-                    // last layer: the norm output is unused (the final norm runs on the sampled rows)
-                    RUN(fused_add_rms_norm_route_slabs_f16(m->residual, nullptr, m->workspace, S, (long)rows_pad * n_pad, n_pad,
-                                                           next_ln ? next_ln : L.input_ln, c.rms_eps, m->norm_out, nullptr, 0, 0, 0,
-                                                           nullptr, nullptr, nullptr, T, H, s, next_qkv_perm));
-                }
-                }
-                qkv_in_perm = next_qkv_perm != nullptr;
-            } else {
-            RUN(dense_linear(m, L.o, m->attn_out, m->o_out, T, s, attn_perm));
-            if (sandwich) {
-                RUN(tp_all_reduce(m, m->o_out, (size_t)T * H));
-                // Gemma 3 (llama_family.rs:3357-3421): residual += norm(o, post_attention_layernorm); pre-MLP norm
-                RUN(sandwich_add_rms_norm_f32(m->o_out, L.post_attn_ln, m->residual_f32, L.post_ln, c.rms_eps, m->norm_out, T, H, s, gu_perm));
-            } else {
-                RUN(tp_all_reduce_add_rms_norm(m, m->o_out, m->residual, L.post_ln, c.rms_eps, m->norm_out, T, H, s, gu_perm));
-            }
-            RUN(dense_linear(m, L.gate_up, m->norm_out, m->gate_up_out, T, s, true));
-            if (c.activation == 1) {
-                RUN(fused_gelu_tanh_mul_split_f16(m->gate_up_out, m->act_out, T, I, s));
-            } else {
-                RUN(fused_silu_mul_split_f16(m->gate_up_out, m->act_out, T, I, s));
-            }
-            RUN(dense_linear(m, L.down, m->act_out, m->mlp_out, T, s));
-            if (sandwich) {
-                RUN(tp_all_reduce(m, m->mlp_out, (size_t)T * H));
-                // residual += norm(mlp_out, post_feedforward_layernorm); next layer's input norm rides along
-                RUN(sandwich_add_rms_norm_f32(m->mlp_out, L.post_ffn_ln, m->residual_f32, next_ln, c.rms_eps, m->norm_out, T, H, s, next_qkv_perm));
-            } else if (next_ln) {
-                RUN(tp_all_reduce_add_rms_norm(m, m->mlp_out, m->residual, next_ln, c.rms_eps, m->norm_out, T, H, s, next_qkv_perm));
-            } else {
-                RUN(tp_all_reduce(m, m->mlp_out, (size_t)T * H));
-                RUN(add_inplace_f16(m->residual, m->mlp_out, (long)T * H, s));
-            }
-            qkv_in_perm = next_ln && next_qkv_perm != nullptr;
-            }
-        }
-        if (m->taps_enabled && m->taps) {
-            if (sandwich)
-                FH_CHECK_HIP(hipMemcpyAsync(m->taps + (size_t)li * c.max_tokens * H, m->residual_f32, (size_t)T * H * 4,
-                                            hipMemcpyDeviceToDevice, s));
-            else
-                hipLaunchKernelGGL(f16_to_f32_kernel, dim3(cdiv((long)T * H, 256)), dim3(256), 0, s, m->residual,
-                                   m->taps + (size_t)li * c.max_tokens * H, (long)T * H);
-        }
+        return 0;
     }
-    m->taps_tokens = T;
-    if (sh.num_sampled > 0) {
-        // final norm + lm_head on the sampled rows only (same rows the reference packs,
-        // qwen3_moe_forward_unified.rs:365-392)
-        if (sandwich) {
-            RUN(rms_norm_f32_to_f16(m->residual_f32, sampled_idx, m->final_norm, c.rms_eps, m->sampled_hidden, sh.num_sampled, H, s));
-        } else {
-            RUN(gather_rms_norm_f16(m->residual, sampled_idx, m->final_norm, c.rms_eps, m->sampled_hidden, sh.num_sampled, H, s));
+    // paged attention over the sequences [first, first + n_seqs) of the batch, which bring `tokens` query rows
+    int varlen_attention(int window, int first, int n_seqs, int tokens, int max_q_len) {
+        const int mb = m->max_blocks_per_seq;
+        return paged_varlen_attention_f16(m->q_out, Lp->k_pool, Lp->v_pool, m->attn_out, ix.cu + first, ix.pos + first, ix.bt + (size_t)first * mb,
+                                          n_seqs, tokens, max_q_len, sh.max_kv_len, nq, nkv, hd, window, KV_BLOCK, mb, m->workspace,
+                                          m->workspace_bytes, s);
+    }
+
+    // expert parallel: after routing, the pair ids become local ids (−1 = another rank's expert)
+    int after_route(int P) {
+        return c.expert_parallel ? moe_remap_expert_ids(m->expert_ids, m->expert_ids_local, P, m->ep_e0, m->ep_E, s) : 0;
+    }
+    // the MoE layer tail: residual_out = residual_in + Σ_k w_k·down_k, then the next input norm.  Expert parallel: the sum over
+    // the rank's own experts is a partial [T, H] that meets the other ranks' in the all-reduce a dense MLP uses, and the
+    // reduced row then enters the residual like a single expert row of weight 1 (the same kernel, top_k = 1)
+    int moe_tail(const __half* res_in, __half* res_out) {
+        const __half* rows = m->moe_down;
+        const float* w = m->expert_w;
+        int K = c.top_k;
+        if (c.expert_parallel) {
+            RUN(moe_combine_local_f16(rows, w, m->expert_ids_local, m->mlp_out, T, K, H, s));
+            RUN(tp_all_reduce(m, m->mlp_out, (size_t)T * H));
+            rows = m->mlp_out; w = m->ones; K = 1;
         }
+        RUN(moe_combine_add_rms_norm_f16(rows, w, res_in, res_out, next_ln, c.rms_eps, m->norm_out, T, K, H, s, next_qkv_perm));
+        qkv_in_perm = next_in_perm();
+        return 0;
+    }
+
+    // o_proj → add/norm/route → grouped GEMMs → tail
+    int moe_mlp(bool attn_perm) {
+        const LayerWeights& L = *Lp;
+        const int E = c.num_experts, K = c.top_k, P = T * K, tiles = (E + 15) / 16, Q = chain_route_parts(m);
+        // attention heads sharded, o_proj row-parallel: all-reduce before the add + norm + route kernel (expert_parallel 2 keeps
+        // attention replicated: full heads on every rank, nothing to reduce there)
+        const bool tp = c.tp_world > 1 && c.expert_parallel != 2;
+        const bool o_quant = L.o.qw != nullptr;           // the slab forms are INT4 kernels; an unquantised o_proj takes the direct GEMM
+        if (T <= 64 && P <= 1024 && K <= 8 && Q >= 1 && tiles / Q <= 8 && (!L.o.perm || attn_perm)) return moe_mlp_decode_fast(attn_perm, tp, Q);
+        // short prefill / a prompt riding along with the decode batch: o_proj as fp32 split-K slabs straight into the
+        // add + norm + route kernel (no reduce launch)
+        const bool o_slabs = T >= 64 && T < m->route_gemm_min_tokens && !tp && o_quant && !L.o.perm && !L.o.bias && m->o_slabs > 0;
+        return moe_mlp_batch(attn_perm, tp, o_slabs);
+    }
+    // decode-fast o_proj: fp32 split-K slabs, reduced inside the next kernel (no reduce launch), where a slab form applies
+    int o_proj_decode_fast(bool attn_perm, bool tp, Slabs* o) {
+        LayerWeights& L = *Lp;
+        o->S = m->o_slabs;
+        if (tp || !L.o.qw) {
+            RUN(dense_linear(m, L.o, m->attn_out, m->o_out, T, s, attn_perm));
+            if (tp) RUN(tp_all_reduce(m, m->o_out, (size_t)T * H));
+            o->S = 0;
+        } else if (o->S > 0 && T > 16 && T <= 32 && !L.o.bias) {
+            if (L.o.perm) form_hit(FORM_PERM_PRODUCER);          // (attn_perm: the decode attention wrote the permuted rows)
+            // 17–32 rows: activations staged once per workgroup in LDS (a wave fetching its own fragments pulls 2× the
+            // weight bytes from L2); decode c=32 4.60 → 4.57 ms per step
+            RUN(w4_gemm_dense_slabs_lds(L.o, m->attn_out, m->workspace, m->workspace_bytes, T, &o->S, &o->rows_pad, &o->n_pad, s));
+            o->base = m->workspace;
+        } else if (o->S > 0) {
+            if (L.o.perm) form_hit(FORM_PERM_PRODUCER);
+            RUN(w4_gemm_dense_slabs(L.o, m->attn_out, m->workspace, m->workspace_bytes, T, o->S, &o->rows_pad, &o->n_pad, s));
+            o->base = m->workspace;
+            o->S = std::min(o->S, L.o.G);
+        } else {
+            RUN(dense_linear(m, L.o, m->attn_out, m->o_out, T, s, attn_perm));
+        }
+        return 0;
+    }
+    int moe_mlp_decode_fast(bool attn_perm, bool tp, int Q) {
+        LayerWeights& L = *Lp;
+        const int E = c.num_experts, K = c.top_k, P = T * K;
+        Slabs o;
+        RUN(o_proj_decode_fast(attn_perm, tp, &o));
+        form_hit(Q > 1 ? FORM_ROUTE_SPLIT : FORM_ROUTE_FUSED);
+        if (Q > 1) {
+            // B over Q expert parts per token (one CU pulls the 512-KB router at ≈70 GB/s; Q CUs share it):
+            // residual → residual2 (ping-pong), norm_out; each token's last-arriving part merges the Q
+            // candidate lists inside the launch and writes expert_ids / expert_w.
+            RUN(fused_add_rms_norm_route_split_f16(m->residual, m->residual2, m->o_out, o.base, o.S, o.stride(), o.n_pad, L.post_ln, c.rms_eps,
+                                                   m->norm_out, L.router, E, K, Q, m->route_cand, m->route_stats, m->route_arrive,
+                                                   c.norm_topk_prob, m->expert_ids, m->expert_w, nullptr, T, H, s));
+        } else {
+            RUN(fused_add_rms_norm_route_slabs_f16(m->residual, m->o_out, o.base, o.S, o.stride(), o.n_pad, L.post_ln, c.rms_eps, m->norm_out,
+                                                   L.router, E, K, c.norm_topk_prob, m->expert_ids, m->expert_w, nullptr, T, H, s));
+        }
+        RUN(after_route(P));
+        RUN(moe_decode_gemms(m, L, P, moe_max_blocks(P, E), s));
+        if (Q > 1 && T <= m->fuse_tail_max_rows && next_ln && !m->taps_enabled && !c.expert_parallel &&
+            w4_gemm_dense_can_fuse_combine_norm(m->layers[li + 1].qkv, T)) {
+            tail = FusedCombineNorm{m->moe_down, m->expert_w, m->residual2, m->residual, next_ln, c.rms_eps, K};
+            pending_tail = true;
+        } else {
+            RUN(moe_tail(Q > 1 ? m->residual2 : m->residual, m->residual));
+        }
+        return 0;
+    }
+    int moe_mlp_batch(bool attn_perm, bool tp, bool o_slabs) {
+        LayerWeights& L = *Lp;
+        const int E = c.num_experts, K = c.top_k, P = T * K;
+        if (o_slabs) {
+            Slabs o{m->workspace, 1};
+            RUN(w4_gemm_dense_slabs_tile(L.o, m->attn_out, m->workspace, m->workspace_bytes, T, &o.S, &o.rows_pad, &o.n_pad, s));
+            RUN(fused_add_rms_norm_route_slabs_f16(m->residual, m->o_out, o.base, o.S, o.stride(), o.n_pad, L.post_ln, c.rms_eps, m->norm_out,
+                                                   L.router, E, K, c.norm_topk_prob, m->expert_ids, m->expert_w, nullptr, T, H, s));
+        } else {
+            RUN(dense_linear(m, L.o, m->attn_out, m->o_out, T, s, attn_perm));
+            if (tp) RUN(tp_all_reduce(m, m->o_out, (size_t)T * H));
+            form_hit(T >= m->route_gemm_min_tokens ? FORM_ROUTE_GEMM : FORM_ROUTE_FUSED);
+            if (T < m->route_gemm_min_tokens) {
+                // residual += o; post-attention norm; router logits; top-k — one launch (fused.hip B)
+                RUN(fused_add_rms_norm_route_f16(m->residual, m->o_out, L.post_ln, c.rms_eps, m->norm_out, L.router, E, K,
+                                                 c.norm_topk_prob, m->expert_ids, m->expert_w, nullptr, T, H, s));
+            } else {
+                // prefill: one workgroup per token would pull the whole router (E·H·2 B) from L2 per token (2048 tokens:
+                // 1 GB, 95 µs) — run the router as a GEMM over all tokens instead, then the top-k kernel
+                RUN(fused_add_rms_norm_f16(m->residual, m->o_out, L.post_ln, c.rms_eps, m->norm_out, T, H, s));
+                if (knobs().route_gemm_topk && !m->taps_enabled && moe_route_gemm_topk_supports(E, H, K)) {
+                    // … and the top-k in the same workgroups: the logits stay on the CU (8192 tokens: 27 + 7 + 16 µs → one launch)
+                    form_hit(FORM_ROUTE_GEMM_TOPK);
+                    RUN(moe_route_gemm_topk_f16(m->norm_out, L.router, m->expert_ids, m->expert_w, T, E, H, K, c.norm_topk_prob, s));
+                } else {
+                    RUN(f16t_gemm_f32out(m->norm_out, L.router, m->router_logits, T, E, H, m->workspace, m->workspace_bytes, s));
+                    RUN(moe_route_topk_softmax_f32(m->router_logits, m->expert_ids, m->expert_w, T, E, K, c.norm_topk_prob, s));
+                }
+            }
+        }
+        RUN(after_route(P));
+        RUN(moe_batch_gemms(m, L, P, P + E * 16, moe_max_blocks(P, E), s));
+        RUN(moe_tail(m->residual, m->residual));
+        return 0;
+    }
+
+    // ── dense MLP block ──
+    // gate_up → gated activation: as split-K slabs that the activation sums, or GEMM + activation (gate_up's input arrives
+    // permuted from its producer where it is act-order)
+    int gate_up_act(bool slabs) {
+        const int I = c.intermediate;
+        Slabs g{m->workspace};
+        if (slabs) {
+            RUN(w4_gemm_dense_slabs_lds(Lp->gate_up, m->norm_out, m->workspace, m->workspace_bytes, T, &g.S, &g.rows_pad, &g.n_pad, s));
+            RUN(fused_gated_act_slabs_f16(g.base, g.S, g.stride(), g.n_pad, m->act_out, T, I, c.activation == 1, s));
+            return 0;
+        }
+        RUN(dense_linear(m, Lp->gate_up, m->norm_out, m->gate_up_out, T, s, true));
+        if (c.activation == 1) RUN(fused_gelu_tanh_mul_split_f16(m->gate_up_out, m->act_out, T, I, s));
+        else RUN(fused_silu_mul_split_f16(m->gate_up_out, m->act_out, T, I, s));
+        return 0;
+    }
+    // the MLP as an op chain: gate_up → gated activation → down
+    int dense_mlp_ops() {
+        RUN(gate_up_act(false));
+        RUN(dense_linear(m, Lp->down, m->act_out, m->mlp_out, T, s));
+        return 0;
+    }
+    // A branch output x (o_proj or down: row-parallel partials under tensor parallelism) is all-reduced and enters the residual, and
+    // the norm that follows rides along.  Sandwich norms (Gemma 3, llama_family.rs:3357-3421): residual_f32 += norm(x, post_norm).
+    // Behind the last layer a plain add (the final norm runs on the sampled rows).  `perm`: act-order permutation of norm_out's reader
+    int dense_tail(__half* x, __half* residual, const __half* post_norm, const __half* next_norm, const int32_t* perm) {
+        if (sandwich) {
+            RUN(tp_all_reduce(m, x, (size_t)T * H));
+            RUN(sandwich_add_rms_norm_f32(x, post_norm, m->residual_f32, next_norm, c.rms_eps, m->norm_out, T, H, s, perm));
+        } else if (next_norm) {
+            RUN(tp_all_reduce_add_rms_norm(m, x, residual, next_norm, c.rms_eps, m->norm_out, T, H, s, perm));
+        } else {
+            RUN(tp_all_reduce(m, x, (size_t)T * H));
+            RUN(add_inplace_f16(residual, x, (long)T * H, s));
+        }
+        return 0;
+    }
+    // the same for a branch output that arrives as split-K slabs (one GPU): the add + norm kernel sums them.  Behind the last
+    // layer the norm output is unused (any valid weight will do)
+    int slab_tail(const Slabs& x, __half* residual, const __half* post_norm, const __half* next_norm, const int32_t* perm) {
+        if (sandwich) {
+            RUN(sandwich_add_rms_norm_f32_slabs(x.base, x.S, x.stride(), x.n_pad, post_norm, m->residual_f32, next_norm, c.rms_eps, m->norm_out,
+                                                T, H, s, perm));
+        } else {
+            RUN(fused_add_rms_norm_route_slabs_f16(residual, nullptr, x.base, x.S, x.stride(), x.n_pad, next_norm ? next_norm : Lp->input_ln,
+                                                   c.rms_eps, m->norm_out, nullptr, 0, 0, 0, nullptr, nullptr, nullptr, T, H, s, perm));
+        }
+        return 0;
+    }
+    int dense_mlp(bool attn_perm) {
+        LayerWeights& L = *Lp;
+        const int32_t* gu_perm = L.gate_up.perm;
+        // 17–32 rows, one GPU: every projection of the MLP block writes fp32 split-K slabs (LDS-shared activations) and
+        // the consumer that exists anyway — add+norm, gated activation — sums them: no reduce launches.
+        // Tensor parallel (o / down row-parallel): the partial sums of the ranks meet in an all-reduce, so those two
+        // projections produce fp16 partials (GEMM + reduce), all-reduce, then add + norm; the column-parallel gate_up keeps
+        // its slabs → gated-activation form.  Everything stays stream-ordered device work, so the step is still one graph.
+        const bool tp = c.tp_world > 1;
+        // (act-order projections: every input of the chain arrives permuted from its producer — decode attention, the norms
+        // below, gate_up's column order)
+        const bool slab_chain = m->dense_slabs && T > 16 && T <= 32 && (!L.o.perm || attn_perm) && (!L.down.perm || L.down.perm_folded) &&
+                                L.o.qw && L.gate_up.qw && L.down.qw;   // INT4 slab kernels; unquantised projections take the op chain
+        const bool slabs = slab_chain && !tp;         // … o_proj and down hand their consumer slabs
+        if (slab_chain) form_hit(FORM_DENSE_SLAB_CHAIN);
+        if (slabs) {
+            Slabs o{m->workspace};
+            if (L.o.perm) form_hit(FORM_PERM_PRODUCER);
+            RUN(w4_gemm_dense_slabs_lds(L.o, m->attn_out, m->workspace, m->workspace_bytes, T, &o.S, &o.rows_pad, &o.n_pad, s));
+            RUN(slab_tail(o, m->residual, L.post_attn_ln, L.post_ln, gu_perm));
+        } else {
+            RUN(dense_linear(m, L.o, m->attn_out, m->o_out, T, s, attn_perm));
+            RUN(dense_tail(m->o_out, m->residual, L.post_attn_ln, L.post_ln, gu_perm));
+        }
+        if (slab_chain && gu_perm) form_hit(FORM_PERM_PRODUCER);
+        if (slab_chain && L.down.perm) form_hit(FORM_PERM_PRODUCER);
+        RUN(gate_up_act(slab_chain));
+        if (slabs) {
+            Slabs down{m->workspace};
+            RUN(w4_gemm_dense_slabs_lds(L.down, m->act_out, m->workspace, m->workspace_bytes, T, &down.S, &down.rows_pad, &down.n_pad, s));
+            RUN(slab_tail(down, m->residual, L.post_ffn_ln, next_ln, next_qkv_perm));
+        } else {
+            RUN(dense_linear(m, L.down, m->act_out, m->mlp_out, T, s));
+            RUN(dense_tail(m->mlp_out, m->residual, L.post_ffn_ln, next_ln, next_qkv_perm));
+        }
+        qkv_in_perm = next_in_perm();
+        return 0;
+    }
+
+    // the residual stream behind this layer, for ferrum_hip_model_read_taps
+    int tap() {
+        if (!m->taps_enabled || !m->taps) return 0;
+        float* dst = m->taps + (size_t)li * c.max_tokens * H;
+        if (sandwich) FH_CHECK_HIP(hipMemcpyAsync(dst, m->residual_f32, (size_t)T * H * 4, hipMemcpyDeviceToDevice, s));
+        else hipLaunchKernelGGL(f16_to_f32_kernel, dim3(cdiv((long)T * H, 256)), dim3(256), 0, s, m->residual, dst, (long)T * H);
+        return 0;
+    }
+
+    // final norm + lm_head on the sampled rows only (same rows the reference packs, qwen3_moe_forward_unified.rs:365-392), then
+    // the greedy argmax on the device
+    int sample_head(bool greedy, const GreedyDeviceOpts* gopts, const DecodeAdvance* advance, int* advance_fused) {
+        const int n = sh.num_sampled;
+        if (n <= 0) return 0;
+        if (sandwich) RUN(rms_norm_f32_to_f16(m->residual_f32, ix.sampled_idx, m->final_norm, c.rms_eps, m->sampled_hidden, n, H, s));
+        else RUN(gather_rms_norm_f16(m->residual, ix.sampled_idx, m->final_norm, c.rms_eps, m->sampled_hidden, n, H, s));
         const int Vn = m->vp_n, v0 = m->vp_v0;                  // this rank's vocabulary rows (all of them unless vocabulary parallel)
-        RUN(f16t_gemm_f32out(m->sampled_hidden, m->lm_head_t, m->logits, sh.num_sampled, Vn, H, m->workspace,
-                             m->workspace_bytes, s));
-        if (greedy && !c.vocab_parallel) {
+        RUN(f16t_gemm_f32out(m->sampled_hidden, m->lm_head_t, m->logits, n, Vn, H, m->workspace, m->workspace_bytes, s));
+        if (!greedy) return 0;
+        const bool penalties = gopts && gopts->row_offsets;
+        if (!c.vocab_parallel) {
             // LogitsReturnPolicy::GreedyArgmax { token_mask, repetition_penalty } (model_executor.rs:109-150): the sparse
             // penalty rewrites the listed logits in place, then raw or masked argmax (traits.rs:1571-1591)
-            if (gopts && gopts->row_offsets)
-                RUN(apply_repetition_penalties_sparse_f32(m->logits, gopts->row_offsets, gopts->token_ids, gopts->penalties,
-                                                          sh.num_sampled, c.vocab, s));
-            RUN(argmax_rows_f32_ws_advance(m->logits, m->out_tokens, gopts ? gopts->mask : nullptr, gopts ? gopts->mask_len : 0,
-                                           sh.num_sampled, c.vocab, m->workspace, m->workspace_bytes, advance, advance_fused, s));
-        } else if (greedy) {
-            // vocabulary parallel: penalty and mask act on the rank's slice (ids / mask bytes shifted by v0), the local first
-            // maximum becomes a (logit, global id) pair, the pairs of all ranks are gathered and the first maximum in rank
-            // order wins — the lowest id among equal logits, as on one GPU.  The merge also advances the decode state.
-            if (gopts && gopts->row_offsets)
-                RUN(apply_repetition_penalties_sparse_f32_shard(m->logits, gopts->row_offsets, gopts->token_ids, gopts->penalties,
-                                                                sh.num_sampled, Vn, v0, s));
-            const uint8_t* mask = gopts && gopts->mask ? gopts->mask + std::min(v0, gopts->mask_len) : nullptr;
-            const int mask_len = gopts && gopts->mask ? std::max(0, gopts->mask_len - v0) : 0;
-            RUN(argmax_rows_f32_ws(m->logits, m->out_tokens, mask, mask_len, sh.num_sampled, Vn, m->workspace, m->workspace_bytes, s));
-            RUN(argmax_pairs_f32(m->logits, m->out_tokens, m->vp_pairs, sh.num_sampled, Vn, v0, mask, mask_len, s));
-            RUN(tp_all_gather(m, m->vp_pairs, m->vp_gathered, (size_t)sh.num_sampled * 8));
-            RUN(argmax_merge_ranks(m->vp_gathered, m->out_tokens, sh.num_sampled, c.tp_world, advance, s));
-            if (advance && advance_fused) *advance_fused = 1;
+            if (penalties) RUN(apply_repetition_penalties_sparse_f32(m->logits, gopts->row_offsets, gopts->token_ids, gopts->penalties, n, c.vocab, s));
+            RUN(argmax_rows_f32_ws_advance(m->logits, m->out_tokens, gopts ? gopts->mask : nullptr, gopts ? gopts->mask_len : 0, n, c.vocab,
+                                           m->workspace, m->workspace_bytes, advance, advance_fused, s));
+            return 0;
         }
+        // vocabulary parallel: penalty and mask act on the rank's slice (ids / mask bytes shifted by v0), the local first
+        // maximum becomes a (logit, global id) pair, the pairs of all ranks are gathered and the first maximum in rank
+        // order wins — the lowest id among equal logits, as on one GPU.  The merge also advances the decode state.
+        if (penalties)
+            RUN(apply_repetition_penalties_sparse_f32_shard(m->logits, gopts->row_offsets, gopts->token_ids, gopts->penalties, n, Vn, v0, s));
+        const uint8_t* mask = gopts && gopts->mask ? gopts->mask + std::min(v0, gopts->mask_len) : nullptr;
+        const int mask_len = gopts && gopts->mask ? std::max(0, gopts->mask_len - v0) : 0;
+        RUN(argmax_rows_f32_ws(m->logits, m->out_tokens, mask, mask_len, n, Vn, m->workspace, m->workspace_bytes, s));
+        RUN(argmax_pairs_f32(m->logits, m->out_tokens, m->vp_pairs, n, Vn, v0, mask, mask_len, s));
+        RUN(tp_all_gather(m, m->vp_pairs, m->vp_gathered, (size_t)n * 8));
+        RUN(argmax_merge_ranks(m->vp_gathered, m->out_tokens, n, c.tp_world, advance, s));
+        if (advance && advance_fused) *advance_fused = 1;
+        return 0;
     }
+};
 #undef RUN
-    return 0;
+
+// Enqueue one forward: head, the layers — each as one of the chain forms (decided per layer, the next layer's decision known, so
+// that a tail can be left to its launch) or as q|k|v + attention and the MLP block — then the sampling head.
+int enqueue_forward(FerrumHipModel* m, const StepShape& sh, bool greedy, const GreedyDeviceOpts* gopts = nullptr,
+                    const DecodeAdvance* advance = nullptr, int* advance_fused = nullptr) {
+    if (advance_fused) *advance_fused = 0;
+    const int n_layers = m->cfg.num_layers;
+    ForwardPass f(m, sh);
+    FH_TRY(f.head());
+    ChainPlan plan = f.plan_chain(0);
+    for (int li = 0; li < n_layers; li++) {
+        const ChainPlan next = li + 1 < n_layers ? f.plan_chain(li + 1) : ChainPlan();
+        f.begin_layer(li);
+        if (plan.kind == CHAIN_DENSE) {
+            FH_TRY(f.dense_chain_layer(plan.d, next.kind == CHAIN_DENSE));
+        } else if (plan.kind == CHAIN_MOE) {
+            FH_TRY(f.moe_chain_layer(plan.d, next.kind == CHAIN_MOE));
+        } else {
+            bool attn_perm = false;
+            FH_TRY(f.qkv_attention(&attn_perm));
+            FH_TRY(m->cfg.num_experts > 0 ? f.moe_mlp(attn_perm) : f.dense_mlp(attn_perm));
+            FH_TRY(f.tap());           // (the chain forms are never taken with taps on)
+        }
+        plan = next;
+    }
+    m->taps_tokens = sh.m_total;
+    return f.sample_head(greedy, gopts, advance, advance_fused);
 }
+#undef FH_TRY
 
 }  // namespace
 
@@ -1772,26 +1831,19 @@ int ferrum_hip_model_unified_forward_ex(FerrumHipModel* m, const FerrumHipBatchI
     if (int rc = reserve(m, reqs.data(), num_items, nullptr)) return rc;
 
     // index block
-    uint32_t* h_tok = reinterpret_cast<uint32_t*>(m->idx_host + m->il.tokens);
-    uint32_t* h_cu = reinterpret_cast<uint32_t*>(m->idx_host + m->il.cu_seqlens);
-    uint32_t* h_pos = reinterpret_cast<uint32_t*>(m->idx_host + m->il.pos_offsets);
-    uint32_t* h_kvl = reinterpret_cast<uint32_t*>(m->idx_host + m->il.kv_lens);
-    int32_t* h_samp = reinterpret_cast<int32_t*>(m->idx_host + m->il.sampled_idx);
-    int32_t* h_bt = reinterpret_cast<int32_t*>(m->idx_host + m->il.block_tables);
+    const IndexBlock h = index_block(m, m->idx_host);
     int t = 0, j = 0;
     for (int i = 0; i < num_items; i++) {
         const FerrumHipBatchItem& it = items[i];
-        h_cu[i] = (uint32_t)t;
-        memcpy(h_tok + t, it.q_tokens, (size_t)it.num_q_tokens * 4);
+        h.cu[i] = (uint32_t)t;
+        memcpy(h.tokens + t, it.q_tokens, (size_t)it.num_q_tokens * 4);
         t += it.num_q_tokens;
-        h_pos[i] = (uint32_t)it.pos_offset;
-        h_kvl[i] = (uint32_t)(it.pos_offset + it.num_q_tokens);
-        if (it.is_final_chunk) h_samp[j++] = t - 1;
-        const SeqState& st = m->seqs[it.seq_id];
-        int32_t* row = h_bt + (size_t)i * m->max_blocks_per_seq;
-        for (int b = 0; b < m->max_blocks_per_seq; b++) row[b] = b < (int)st.blocks.size() ? (int32_t)st.blocks[b] : 0;   // padded with 0 (paged_pool.rs:438-440)
+        h.pos[i] = (uint32_t)it.pos_offset;
+        h.kvl[i] = (uint32_t)(it.pos_offset + it.num_q_tokens);
+        if (it.is_final_chunk) h.sampled_idx[j++] = t - 1;
+        fill_block_table_row(m, h.bt + (size_t)i * m->max_blocks_per_seq, m->seqs[it.seq_id]);
     }
-    h_cu[num_items] = (uint32_t)t;
+    h.cu[num_items] = (uint32_t)t;
     sh.single_prefix = 0;
     while (sh.single_prefix < num_items && items[sh.single_prefix].num_q_tokens == 1) sh.single_prefix++;
     sh.rest_min_q = 0;
@@ -1885,32 +1937,26 @@ int ferrum_hip_model_decode_steps(FerrumHipModel* m, const uint64_t* seq_ids, co
         FH_CHECK_HIP(hipMalloc((void**)&m->history, (size_t)cap * 4));
         m->history_cap = cap;
     }
-    uint32_t* h_tok = reinterpret_cast<uint32_t*>(m->idx_host + m->il.tokens);
-    uint32_t* h_cu = reinterpret_cast<uint32_t*>(m->idx_host + m->il.cu_seqlens);
-    uint32_t* h_pos = reinterpret_cast<uint32_t*>(m->idx_host + m->il.pos_offsets);
-    uint32_t* h_kvl = reinterpret_cast<uint32_t*>(m->idx_host + m->il.kv_lens);
-    int32_t* h_samp = reinterpret_cast<int32_t*>(m->idx_host + m->il.sampled_idx);
-    int32_t* h_bt = reinterpret_cast<int32_t*>(m->idx_host + m->il.block_tables);
+    const IndexBlock h = index_block(m, m->idx_host);
     for (int i = 0; i < n; i++) {
         const SeqState& st = m->seqs[seq_ids[i]];
-        h_tok[i] = first_tokens[i];
-        h_cu[i] = (uint32_t)i;
-        h_pos[i] = (uint32_t)st.len;
-        h_kvl[i] = (uint32_t)st.len + 1;
-        h_samp[i] = i;
-        int32_t* row = h_bt + (size_t)i * m->max_blocks_per_seq;
-        for (int b = 0; b < m->max_blocks_per_seq; b++) row[b] = b < (int)st.blocks.size() ? (int32_t)st.blocks[b] : 0;
+        h.tokens[i] = first_tokens[i];
+        h.cu[i] = (uint32_t)i;
+        h.pos[i] = (uint32_t)st.len;
+        h.kvl[i] = (uint32_t)st.len + 1;
+        h.sampled_idx[i] = i;
+        fill_block_table_row(m, h.bt + (size_t)i * m->max_blocks_per_seq, st);
     }
-    h_cu[n] = (uint32_t)n;
+    h.cu[n] = (uint32_t)n;
     size_t used = m->il.block_tables + (size_t)n * m->max_blocks_per_seq * 4;
     FH_CHECK_HIP(hipMemcpyAsync(m->idx_dev, m->idx_host, used, hipMemcpyHostToDevice, m->stream));
     FH_CHECK_HIP(hipMemsetAsync(m->step_counter, 0, 8, m->stream));    // step index + the advance ticket
 
     auto enqueue_step = [&]() -> int {
         // the step's bookkeeping (sampled id → next input, positions, history) rides in the last stage of the argmax
+        const IndexBlock d = index_block(m, m->idx_dev);
         DecodeAdvance adv;
-        adv.tokens = idx<uint32_t>(m, m->il.tokens); adv.pos_offsets = idx<uint32_t>(m, m->il.pos_offsets);
-        adv.kv_lens = idx<uint32_t>(m, m->il.kv_lens); adv.history = m->history; adv.step_counter = m->step_counter;
+        adv.tokens = d.tokens; adv.pos_offsets = d.pos; adv.kv_lens = d.kvl; adv.history = m->history; adv.step_counter = m->step_counter;
         adv.ticket = reinterpret_cast<unsigned*>(m->step_counter + 1); adv.n = n;
         int fused = 0;
         if (int rc = enqueue_forward(m, sh, true, nullptr, &adv, &fused)) return rc;
@@ -2000,9 +2046,9 @@ int ferrum_hip_model_time_kernel(FerrumHipModel* m, int which, int n_seqs, int m
     }
     if (moe_blocks) *moe_blocks = blocks;
     FH_REQUIRE(T <= c.max_tokens, "time_kernel: %d rows > max_tokens %d", T, c.max_tokens);
-    const int max_blocks = E > 0 ? std::min((P + E * 16) / 16, P / 16 + std::min(P, E)) : 0;
+    const int max_blocks = E > 0 ? moe_max_blocks(P, E) : 0;
     int launches = 0, rc = 0;
-    const bool em = E > 0 && m->moe_em_min_pairs_x8 > 0 && 8L * P >= (long)m->moe_em_min_pairs_x8 * c.num_experts;   // as moe_decode_gemms
+    const bool em = E > 0 && moe_expert_major(m, P);
     auto one = [&](int li) -> int {
         LayerWeights& L = m->layers[li];
         switch (which) {
@@ -2015,21 +2061,18 @@ int ferrum_hip_model_time_kernel(FerrumHipModel* m, int which, int n_seqs, int m
             if (em) return w4_gemm_moe_expert_major(L.exp_down, m->moe_act, m->moe_down, eids, E, P, 1, 0, s);
             return w4_gemm_moe(L.exp_down, m->moe_act, m->moe_down, m->sorted_ids, m->block_ids, m->total_post_pad, P, max_blocks, 1, 0, s);
         case 8: {   // gate_up → down as the step runs them: one merged launch (falls back to an error when the shapes do not take it)
-            unsigned* cur = m->em2_arrive + (size_t)(launches & 1) * m->arrive_half_words;
-            unsigned* nxt = m->em2_arrive + (size_t)((launches & 1) ^ 1) * m->arrive_half_words;
+            unsigned *cur = arrive_half(m, launches & 1), *nxt = arrive_half(m, (launches & 1) ^ 1);
             int took = 0;
             // (as the step runs it: from the candidate lists the last chain launch left, where that is the layer's form)
-            MoeRouteLists lists;
-            lists.cand = m->route_cand; lists.stats = m->route_stats; lists.T = T; lists.Q = chain_route_parts(m); lists.norm_topk = c.norm_topk_prob;
-            lists.pub_expert_ids = m->expert_ids; lists.pub_expert_w = m->expert_w;
+            const MoeRouteLists lists = route_lists(m, T, chain_route_parts(m));
             const bool from_lists = lists.Q > 1 && knobs().decode_chain && moe_pair_rank_lists_ok(m, L, T, lists.Q);
             if (int r_ = w4_gemm_moe_expert_major_pair(L.exp_gate_up, L.exp_down, m->norm_out, m->moe_act, m->moe_down, eids, E, P, c.top_k,
                                                        cur, nxt, m->inlaunch_timeouts, &took, s, from_lists ? &lists : nullptr)) return r_;
             if (!took) { fh::set_error("time_kernel: the merged gate_up → down launch does not take these shapes"); return FERRUM_HIP_UNSUPPORTED; }
             return 0;
         }
-        case 2: return paged_batched_decode_attention_f16(m->q_out, L.k_pool, L.v_pool, m->attn_out, idx<int32_t>(m, m->il.block_tables),
-                                                          idx<uint32_t>(m, m->il.kv_lens), T, max_kv_len, c.num_heads, c.num_kv_heads,
+        case 2: return paged_batched_decode_attention_f16(m->q_out, L.k_pool, L.v_pool, m->attn_out, index_block(m, m->idx_dev).bt,
+                                                          index_block(m, m->idx_dev).kvl, T, max_kv_len, c.num_heads, c.num_kv_heads,
                                                           c.head_dim, KV_BLOCK, m->max_blocks_per_seq, m->workspace, m->workspace_bytes, s);
         case 3: return w4_gemm_dense(L.qkv, m->norm_out, m->qkv_out, T, m->workspace, m->workspace_bytes, s);
         case 4: return w4_gemm_dense(L.o, m->attn_out, m->o_out, T, m->workspace, m->workspace_bytes, s);

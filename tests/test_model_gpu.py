@@ -1661,3 +1661,35 @@ def test_multi_process_tensor_parallel_rehearsal_over_hipipc(pkg, world):
     assert tp["per_rank_shapes"]["num_kv_heads"] == 8 // world and tp["tok_s"] > 0
     ep = d["ep_decode"]                                           # Qwen3-30B-A3B dims as one expert-parallel group
     assert ep["ranks_agree_on_ids"] and ep["oneshot_timeouts"] == 0 and ep["per_rank_shapes"]["experts"] == 128 // world, ep
+
+
+def test_launch_trace_names_every_step_and_changes_no_result(pkg, knobs, capfd):
+    """FERRUM_HIP_TRACE_LAUNCHES=1 with FERRUM_HIP_NO_GRAPH=1: every step of a forward is named on stderr with its row count and
+    waited for; ids and logits are those of the untraced run bit for bit, and without the knobs nothing is printed.  The tiny
+    two-layer MoE model: a 3-token prefill, a decode step through the unified forward and one through the decode loop."""
+    from tests import modelgen
+    layers = 2
+    tm = modelgen.TinyModel(True, layers=layers, seed=3)
+    prompt = np.random.default_rng(4).integers(0, tm.cfg["vocab"], size=3).astype(np.uint32)
+
+    def run():
+        hm = tm.hip_model(pkg)
+        capfd.readouterr()
+        t0, l0 = hm.unified_forward([(1, prompt, 0, True)], greedy=True, want_logits=True)
+        err_prefill = capfd.readouterr().err
+        t1, l1 = hm.unified_forward([(1, t0[:1], 3, True)], greedy=True, want_logits=True)
+        t2 = hm.decode_steps([1], t1[:1], 1)
+        err_decode = capfd.readouterr().err
+        return (t0, l0, t1, l1, t2), err_prefill, err_decode
+
+    knobs.set(NO_GRAPH=1, TRACE_LAUNCHES=1)
+    traced, err_prefill, err_decode = run()
+    knobs.set(NO_GRAPH=None, TRACE_LAUNCHES=None)
+    plain, quiet_prefill, quiet_decode = run()
+    for a, b in zip(traced, plain):
+        assert a.dtype == b.dtype and a.shape == b.shape and a.tobytes() == b.tobytes()
+    prefill_lines = [ln for ln in err_prefill.splitlines() if ln.startswith("[ferrum_hip] T=3 ")]
+    decode_lines = [ln for ln in err_decode.splitlines() if ln.startswith("[ferrum_hip] T=1 ")]
+    assert len(prefill_lines) >= 2 * layers and "[ferrum_hip] T=1 " not in err_prefill, err_prefill
+    assert len(decode_lines) >= 2 * (2 * layers) and "[ferrum_hip] T=3 " not in err_decode, err_decode      # two forwards
+    assert "[ferrum_hip] T=" not in quiet_prefill + quiet_decode
