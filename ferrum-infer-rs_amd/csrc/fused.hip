@@ -4,7 +4,7 @@
 // the arithmetic is nanoseconds), so the runner merges the chains the reference issues one op at a time
 // (qwen3_moe_forward_unified_layer.rs:380-451):
 //   B  fused_add_rms_norm → router GEMM → route_topk_softmax            → ONE launch per token row
-//      (router weights in the f16t tile layout of w4_gemm.hip, padded to a multiple of 16 experts)
+//      (router weights in the f16t tile layout of f16_gemm.hip, padded to a multiple of 16 experts)
 //   A  moe_combine (weighted_sum) → add_inplace → next layer's rms_norm  → ONE launch per token row
 // The arithmetic per element is unchanged: same rounding points as the unfused HIP ops (residual stored
 // fp16, norm taken from the rounded residual, router logits fp32 from fp16 operands, top-k by k
@@ -220,7 +220,7 @@ int fused_add_rms_norm_route_slabs_f16(__half* residual, const __half* x, const 
 // experts are split over Q workgroups per token.  Every part repeats the (tiny) add + norm of its token,
 // computes the logits of its E/Q experts on the matrix cores and emits its best min(8, E/Q) candidates
 // (sorted by logit, ties → lower id) plus its softmax statistics (max, Σexp).  The consumer — the prologue
-// of the gate_up grouped GEMM — merges the Q sorted lists per token (merge_route_candidates in w4_gemm.hip).
+// of the gate_up grouped GEMM — merges the Q sorted lists per token (merge_route_candidates in w4_skinny.hip).
 // The o-projection may arrive as S fp32 split-K slabs, reduced here in slab order (deterministic).
 template <bool SLABS>
 __global__ __launch_bounds__(512) void add_rmsnorm_route_part_kernel(

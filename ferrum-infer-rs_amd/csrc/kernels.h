@@ -7,10 +7,10 @@
 
 namespace fh {
 
-// one router candidate (fused.hip part kernel → w4_gemm.hip merge)
+// one router candidate (fused.hip part kernel → w4_skinny.hip / w4_moe_em.hip merge)
 struct RouteCand { float logit; int id; };
 
-// ── GPTQ-INT4 (w4_gemm.hip) ──────────────────────────────────────────────────
+// ── GPTQ-INT4 (w4_repack.cc, w4_decode.hip, w4_tiles.hip, w4_skinny.hip, w4_moe_em.hip; fp16: f16_gemm.hip) ──────────────────────────────────────────────────
 struct W4HostPacked {
     int k = 0, n = 0, n64 = 0, G = 0;
     bool symmetric = true;
@@ -103,7 +103,7 @@ int f16_gemm(const __half* x, const __half* w, __half* out, int m, int n, int k,
 int f16_gemm_f32out(const __half* x, const __half* w, float* out, int m, int n, int k, float* workspace,
                     size_t workspace_bytes, hipStream_t stream);
 
-// fp16 weights in MFMA-fragment-major tiles (w4_gemm.hip "f16t"): [N/16][K/32][64 lanes][8]
+// fp16 weights in MFMA-fragment-major tiles (f16_gemm.hip "f16t"): [N/16][K/32][64 lanes][8]
 int f16t_repack(const __half* w_rowmajor, __half* out_tiled, int n, int k, hipStream_t stream);
 size_t f16t_elems(int n, int k);
 int f16t_gemm(const __half* x, const __half* wt, __half* out, int m, int n, int k, float* workspace,

@@ -25,7 +25,7 @@ struct Knobs {
     bool attn_no_resident = false;    // never take the resident-K/V short-prompt prefill form
     long attn_resident_min_wgs = 128; // … and only from this many workgroups (tests lower it)
     bool attn_flash32 = false;        // the flash form with 32-key steps (paged_prefill_attn_kernel) for head_dim 128 too
-    // INT4 GEMMs (w4_gemm.hip)
+    // INT4 GEMMs (w4_decode.hip, w4_tiles.hip, w4_skinny.hip)
     int moe_kw_pairs = 16;
     int decode_chain = 1;             // MoE decode at ≤ 32 rows: tail + q|k|v + attention + o_proj + route as ONE launch (0 = five launches)
     int chain_max_rows = 128;         // decode chain up to this many rows (≤ 128)

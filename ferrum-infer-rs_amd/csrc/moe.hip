@@ -98,7 +98,7 @@ int moe_route_topk_softmax_f32(const float* logits, int32_t* expert_ids, float* 
 
 // ── prefill router in ONE launch: logits = x · Wrᵀ on the matrix cores, then softmax + top-k, 32 tokens per workgroup ──────────
 // Replaces f16t GEMM (split-K 4) → reduce → one-wave-per-token top-k (27 + 7 + 16 µs per layer at 8192 tokens): the logits never
-// leave the CU.  E = 128 (eight 16-expert tiles of the f16t layout, w4_gemm.hip), K split over the four waves (each wave: 32
+// leave the CU.  E = 128 (eight 16-expert tiles of the f16t layout, f16_gemm.hip), K split over the four waves (each wave: 32
 // tokens × 128 experts × K/4), partial sums meet in LDS in wave order; then 16 lanes per token (8 experts each, e = l + 16·i), four
 // tokens per wave pass: f32 softmax over all experts, k argmax-mask passes (strict > within a lane's ascending experts, ties →
 // lower id across lanes), renormalised by the selected sum — router.rs:113-195 / moe_router.cu:32 as moe_route_kernel above.

@@ -1,5 +1,5 @@
 // Merge of a token's Q per-part router candidate lists, one wave, lane-parallel: shared by role B of the decode chain
-// (chain.hip, the parts meet inside the launch) and by the grouped GEMMs that take the lists themselves (w4_gemm.hip).
+// (chain.hip, the parts meet inside the launch) and by the grouped GEMMs that take the lists themselves (w4_skinny.hip, w4_moe_em.hip).
 // Selection order (ferrum-models/src/moe/router.rs:159-178): logit descending, ties → lower expert id; combine weights
 // (router.rs:141-157,180-193): softmax over ALL experts from the parts' (max, Σexp) statistics, optionally renormalised over
 // the K picked, summed in pick order.

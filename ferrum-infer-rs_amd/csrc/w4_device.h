@@ -1,5 +1,5 @@
-// Device-side pieces of the INT4 (w4t) GEMMs shared by the kernel translation units (w4_gemm.hip, chain.hip):
-// in-place nibble expansion and the one-quant-group MFMA step.  Layout and arithmetic: see w4_gemm.hip's header comment.
+// Device-side pieces of the INT4 (w4t) GEMMs shared by the kernel translation units (w4_*.hip, chain.hip):
+// in-place nibble expansion and the one-quant-group MFMA step.  Layout: w4_repack.cc; arithmetic: w4_gemm.h's header comment.
 #pragma once
 #include "common.h"
 
@@ -37,6 +37,13 @@ __device__ __forceinline__ half8 splat_half8(float v) {
     return (half8){h, h, h, h, h, h, h, h};
 }
 
+// half i of four packed fp16 (a lane's group scales / zeros)
+__device__ __forceinline__ _Float16 half_at(unsigned long long bits, int i) {
+    union { uint16_t u; _Float16 h; } c;
+    c.u = (uint16_t)(bits >> (16 * i));
+    return c.h;
+}
+
 // One quant group (128 k) of NT column tiles × MT row tiles.
 //   wq[nt]  : the lane's 4 packed dwords of tile nt          af[mt][s] : activation fragments, k-steps 0..3
 //   acc     : fp32 accumulators                              sbits/zbits: 4 packed fp16 scales / zeros
@@ -52,11 +59,6 @@ __device__ __forceinline__ void w4_consume_group(const WQ (&wq)[NT], unsigned lo
                                                  float4v (&acc)[MT][NT]) {
     const uint32_t magic = opaque_vgpr(0x64006400u), magic_hi = opaque_vgpr(0x54005400u);
     const uint32_t m_lo = opaque_sgpr(0x000F000Fu), m_hi = opaque_sgpr(0x00F000F0u);
-    auto half_at = [](unsigned long long bits, int i) {
-        union { uint16_t u; _Float16 h; } c;
-        c.u = (uint16_t)(bits >> (16 * i));
-        return c.h;
-    };
     float4v neg_off[MT], s_sum[MT];
 #pragma unroll
     for (int mt = 0; mt < MT; mt++) {

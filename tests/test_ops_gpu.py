@@ -913,6 +913,7 @@ def test_moe_grouped_gemm_and_combine(env, tokens, E, K, H, I, forms):
         stack = B.load_gptq_stacked([q for q, _, _ in gu], [s for _, s, _ in gu], [z for _, _, z in gu], None, 4, 128, H,
                                     2 * I, fuse_gate_up=fused)
         act = torch.zeros(P, I, dtype=torch.float16, device="cuda")
+        forms.reset()
         if fused:
             stack.gemm_phase_vllm(ctx, xd, sd, bd, td, act, P, 16, K, max_blocks, fused_silu_mul=True)
         else:
@@ -921,6 +922,7 @@ def test_moe_grouped_gemm_and_combine(env, tokens, E, K, H, I, forms):
             B.fused_silu_mul_split(ctx, gup, act, P, I)
         down = torch.zeros(P, H, dtype=torch.float16, device="cuda")
         down_stack.gemm_phase_vllm(ctx, act, sd, bd, td, down, P, 16, 1, max_blocks)
+        forms.require("moe_block16")
         out = torch.zeros(tokens, H, dtype=torch.float16, device="cuda")
         B.moe_combine(ctx, down, wd, out, tokens, K, H)
         ctx.sync()
@@ -936,8 +938,10 @@ def test_moe_grouped_gemm_and_combine(env, tokens, E, K, H, I, forms):
             mbb = (P + E * blk) // blk
             actb = torch.zeros(P, I, dtype=torch.float16, device="cuda")
             downb = torch.zeros(P, H, dtype=torch.float16, device="cuda")
+            forms.reset()
             stack.gemm_phase_vllm(ctx, xd, sdb, bdb, tdb, actb, P, blk, K, mbb, fused_silu_mul=True)
             down_stack.gemm_phase_vllm(ctx, actb, sdb, bdb, tdb, downb, P, blk, 1, mbb)
+            forms.require({64: "moe_tile64", 32: "moe_tile32"}.get(blk, "moe_tile_big"), absent=("moe_block16",))
             outb = torch.zeros(tokens, H, dtype=torch.float16, device="cuda")
             B.moe_combine(ctx, downb, wd, outb, tokens, K, H)
             ctx.sync()
@@ -949,6 +953,7 @@ def test_moe_grouped_gemm_and_combine(env, tokens, E, K, H, I, forms):
         # (≤ 16 pairs of a K ≥ 512 stack: the block-major launches above split K over four waves — another fp32 summation order)
         same = (lambda x_, y_: torch.equal(x_, y_)) if P > 16 else (lambda x_, y_: nmse(host(x_), host(y_)) < 1e-6)
         down3 = torch.zeros(P, H, dtype=torch.float16, device="cuda")
+        forms.reset()
         if fused:
             act3 = torch.zeros(P, I, dtype=torch.float16, device="cuda")
             stack.gemm_phase_expert_major(ctx, xd, ids_d, act3, P, E, K, fused_silu_mul=True)
@@ -960,6 +965,7 @@ def test_moe_grouped_gemm_and_combine(env, tokens, E, K, H, I, forms):
             ctx.sync()
             assert same(gup, gup3)
         down_stack.gemm_phase_expert_major(ctx, act3 if fused else act, ids_d, down3, P, E, 1)
+        forms.require("moe_expert_major")
         ctx.sync()
         assert same(down, down3)
         if fused and P <= 1024 and I >= 256:
@@ -978,8 +984,10 @@ def test_moe_grouped_gemm_and_combine(env, tokens, E, K, H, I, forms):
             # align computed inside the GEMM from the raw expert ids: bit-identical outputs
             act2 = torch.zeros(P, I, dtype=torch.float16, device="cuda")
             down2 = torch.zeros(P, H, dtype=torch.float16, device="cuda")
+            forms.reset()
             stack.gemm_phase_inline_align(ctx, xd, ids_d, act2, P, E, K, max_blocks, fused_silu_mul=True)
             down_stack.gemm_phase_inline_align(ctx, act2, ids_d, down2, P, E, 1, max_blocks)
+            forms.require("moe_inline_align")
             ctx.sync()
             assert torch.equal(act, act2) and torch.equal(down, down2)
 
