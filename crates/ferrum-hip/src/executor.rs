@@ -196,6 +196,26 @@ impl DecoderOnlyLLM for HipDecoderModel {
             }
         }
     }
+    // common/llm.rs:286 — roll the cache back (speculative rejection, stop-string back-off); new_len ≥ the length is a no-op
+    fn truncate_kv(&mut self, cache_id: &str, new_len: usize) {
+        let Some(&id) = self.ids.get(cache_id) else { panic!("truncate_kv: unknown cache {cache_id}") };
+        if unsafe { ffi::ferrum_hip_model_truncate_kv(self.m, id, new_len as c_int) } != ffi::FERRUM_HIP_OK {
+            panic!("truncate_kv: {}", last_error());
+        }
+        if let Some(l) = self.lens.get_mut(cache_id) {
+            *l = (*l).min(new_len);
+        }
+    }
+    // common/llm.rs:207 — the documented fallback, a loop of single-token full-logits forwards, but starting at the cache's own
+    // end: the trait's default starts at position 0 and would overwrite a live sequence
+    fn forward_verify(&mut self, cache_id: &str, tokens: &[u32]) -> Vec<f32> {
+        let start = self.lens.get(cache_id).copied().unwrap_or(0);
+        let mut out = Vec::with_capacity(tokens.len() * self.local_vocab());
+        for (i, &tok) in tokens.iter().enumerate() {
+            out.extend_from_slice(&self.decode(cache_id, tok, (start + i) as u32));
+        }
+        out
+    }
     fn reset(&mut self) {
         let ids: Vec<String> = self.ids.keys().cloned().collect();
         for c in ids {

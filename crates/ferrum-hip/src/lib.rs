@@ -107,5 +107,6 @@ pub const TRAIT_MAP: &[(&str, &str, &str, &str)] = &[
     ("DecoderOnlyLLM", "kv_slot_capacity_snapshot", "common/llm.rs:141", "ferrum_hip_model_kv_capacity_snapshot"),
     ("DecoderOnlyLLM", "unified_forward_with_logits_policy", "common/llm.rs:260", "ferrum_hip_model_unified_forward_ex"),
     ("DecoderOnlyLLM", "release", "common/llm.rs:278", "ferrum_hip_model_release"),
+    ("DecoderOnlyLLM", "truncate_kv", "common/llm.rs:286", "ferrum_hip_model_truncate_kv"),
     ("ModelExecutor", "unified_decode", "model_executor.rs:567", "ferrum_hip_model_unified_forward_ex"),
 ];

@@ -758,6 +758,13 @@ int ferrum_hip_paged_kv_read_f16(const void* cache_k, const void* cache_v, const
                              H(v_out), ST(stream));
 }
 
+int ferrum_hip_kv_move_blocks(const void* const* pools_dev, int num_pools, const uint32_t* pairs_dev, int num_pairs, void* staging_dev,
+                              size_t chunk_bytes, int num_blocks, int mode, void* stream) {
+    FH_REQUIRE(((uintptr_t)staging_dev & 15) == 0, "kv_move_blocks: staging buffer is not 16-byte aligned");
+    return kv_move_blocks(const_cast<void* const*>(pools_dev), num_pools, pairs_dev, num_pairs, staging_dev, chunk_bytes, num_blocks, mode,
+                          ST(stream));
+}
+
 // ── MoE routing ─────────────────────────────────────────────────────────────
 int ferrum_hip_moe_route_topk_softmax_f16(const void* logits, int32_t* ids, float* w, int tokens, int num_experts,
                                           int top_k, int norm, void* stream) {

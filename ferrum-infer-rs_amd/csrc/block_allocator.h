@@ -140,6 +140,7 @@ public:
     uint32_t free_count() const { return (uint32_t)free_list_.size(); }
     uint32_t capacity() const { return capacity_; }
     uint32_t ref_count(uint32_t b) const { return ref_counts_[b]; }
+    bool has_hash(uint32_t b) const { return has_hash_[b] != 0; }   // the block is a prefix-cache entry (live or soft-free)
     uint32_t peak_in_use() const { return peak_; }
     uint32_t hash_table_size() const { return (uint32_t)table_.size(); }
 

@@ -184,6 +184,14 @@ int paged_batched_decode_attention_f16(const __half* q, const __half* k_pool, co
                                        hipStream_t s, const int32_t* out_scatter = nullptr);
 size_t paged_attention_workspace_bytes(int total_q_tokens, int num_heads, int head_dim, int max_kv_len);
 
+// ── whole-block KV moves (kv_move.hip): fork / truncate / host swap ──────────
+// pools_dev: device array of num_pools pool base pointers (a model's are K0, V0, K1, V1, …), every pool [num_blocks][chunk_bytes];
+// pairs_dev: device array of num_pairs (src_block, dst_block) u32 pairs — gather reads .src only, scatter .dst only;
+// staging (gather / scatter): [num_pairs][num_pools][chunk_bytes], 16-byte aligned like the pools.
+enum KvMoveMode { KV_MOVE_POOL = 0, KV_MOVE_GATHER = 1, KV_MOVE_SCATTER = 2 };
+int kv_move_blocks(void* const* pools_dev, int num_pools, const uint32_t* pairs_dev, int num_pairs, void* staging, size_t chunk_bytes,
+                   int num_blocks, int mode, hipStream_t s);
+
 // ── MoE routing (moe.hip) ────────────────────────────────────────────────────
 int moe_route_topk_softmax_f16(const __half* logits, int32_t* expert_ids, float* expert_weights, int tokens,
                                int num_experts, int top_k, int norm_topk_prob, hipStream_t s);

@@ -70,6 +70,12 @@ struct FerrumHipModel {
     std::unique_ptr<fh::BlockAllocator> alloc;
     std::unordered_map<uint64_t, fh::SeqState> seqs;
     uint64_t prefix_hits = 0, prefix_misses = 0, prefix_saved_tokens = 0;   // block-level prefix cache probes
+    // whole-block KV moves (kv_move.hip) behind fork / truncate_kv / kv_swap_out / kv_swap_in
+    void** kv_pools_dev = nullptr;        // [2·L] pool base pointers K0, V0, K1, V1, … (built once at finalize)
+    uint32_t* kv_pairs_dev = nullptr;     // (src block, dst block) list of the current move; grows on demand
+    size_t kv_pairs_cap = 0;              // … in pairs
+    uint8_t* kv_staging = nullptr;        // gather / scatter side of a host swap: grows on demand up to KV_STAGING_CAP_BYTES
+    size_t kv_staging_bytes = 0;          //   (these calls are host-synchronous and never run inside a capture)
 
     // scratch
     __half *residual = nullptr, *norm_out = nullptr, *qkv_out = nullptr, *q_out = nullptr, *attn_out = nullptr,

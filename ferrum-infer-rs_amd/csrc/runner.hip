@@ -404,7 +404,8 @@ int ferrum_hip_model_destroy(FerrumHipModel* m) {
                     (void*)m->idx_dev, (void*)m->history, (void*)m->step_counter, (void*)m->residual2, (void*)m->chain_o_part, (void*)m->chain_attn_partial, (void*)m->chain_attn_tickets,
                     (void*)m->route_cand, (void*)m->route_stats, (void*)m->route_arrive, (void*)m->cos_local,
                     (void*)m->sin_local, (void*)m->residual_f32, (void*)m->gather_scratch, (void*)m->greedy_opts_dev, (void*)m->tp_tmp,
-                    (void*)m->expert_ids_local, (void*)m->ones, m->vp_pairs, m->vp_gathered})
+                    (void*)m->expert_ids_local, (void*)m->ones, m->vp_pairs, m->vp_gathered,
+                    (void*)m->kv_pools_dev, (void*)m->kv_pairs_dev, (void*)m->kv_staging})
         if (p) (void)hipFree(p);
     if (m->idx_host) (void)hipHostFree(m->idx_host);
     if (m->inlaunch_timeouts) (void)hipHostFree(m->inlaunch_timeouts);
@@ -738,6 +739,12 @@ int ferrum_hip_model_finalize(FerrumHipModel* m) {
         if (int rc = dev_alloc(&L.k_pool, elems)) return rc;
         if (int rc = dev_alloc(&L.v_pool, elems)) return rc;
     }
+    {   // the pools as one device pointer array (K0, V0, K1, V1, …): what a whole-block KV move indexes by grid row
+        std::vector<void*> pools;
+        for (auto& L : m->layers) { pools.push_back(L.k_pool); pools.push_back(L.v_pool); }
+        FH_CHECK_HIP(hipMalloc((void**)&m->kv_pools_dev, pools.size() * sizeof(void*)));
+        FH_CHECK_HIP(hipMemcpy(m->kv_pools_dev, pools.data(), pools.size() * sizeof(void*), hipMemcpyHostToDevice));
+    }
     int rc = 0;
     rc |= dev_alloc(&m->residual, T * H);
     if (c.sandwich_norms) rc |= dev_alloc(&m->residual_f32, T * H);
@@ -1008,6 +1015,204 @@ int ferrum_hip_model_read_kv_f32(FerrumHipModel* m, uint64_t seq_id, int layer, 
     }
     (void)hipFree(kd); (void)hipFree(vd); (void)hipFree(fd); (void)hipFree(bt);
     return rc;
+}
+
+// ── sequence KV lifecycle: truncate, copy-on-write fork, host swap (include/ferrum_hip.h) ──────────────────────────────
+// All of it is whole-block copying (kv_move.hip) plus allocator bookkeeping.  Every call validates and allocates first, moves,
+// waits for the stream, and only then commits the host state: a failure returns with the model as it was.
+static size_t kv_chunk_bytes(const FerrumHipModelConfig& c) { return (size_t)c.num_kv_heads * kv_tile_elems(c.head_dim) * sizeof(__half); }
+static size_t kv_block_bytes(const FerrumHipModelConfig& c) { return kv_chunk_bytes(c) * 2 * (size_t)c.num_layers; }   // every layer, K and V
+constexpr size_t KV_STAGING_CAP_BYTES = (size_t)64 << 20;   // a longer sequence swaps in block ranges of this size
+constexpr size_t KV_SWAP_HEADER_BYTES = 32;
+constexpr uint32_t KV_SWAP_MAGIC = 0x564B4846u, KV_SWAP_VERSION = 1u;   // "FHKV"
+
+// pairs: (src, dst) u32 pairs of one move, uploaded through the growable device list.  The caller waits for the stream before
+// `pairs` goes away.
+static int kv_move(FerrumHipModel* m, const std::vector<uint32_t>& pairs, int mode) {
+    const size_t n = pairs.size() / 2;
+    if (!n) return 0;
+    if (m->kv_pairs_cap < n) {
+        FH_CHECK_HIP(hipStreamSynchronize(m->stream));
+        if (m->kv_pairs_dev) (void)hipFree(m->kv_pairs_dev);
+        m->kv_pairs_dev = nullptr;
+        m->kv_pairs_cap = 0;
+        const size_t cap = std::max<size_t>(n, 256);
+        FH_CHECK_HIP(hipMalloc((void**)&m->kv_pairs_dev, cap * 8));
+        m->kv_pairs_cap = cap;
+    }
+    FH_CHECK_HIP(hipMemcpyAsync(m->kv_pairs_dev, pairs.data(), n * 8, hipMemcpyHostToDevice, m->stream));
+    return kv_move_blocks(m->kv_pools_dev, 2 * m->cfg.num_layers, m->kv_pairs_dev, (int)n, m->kv_staging, kv_chunk_bytes(m->cfg),
+                          m->cfg.kv_num_blocks, mode, m->stream);
+}
+
+// pool → pool copy of one block of every layer, finished when this returns
+static int kv_copy_block(FerrumHipModel* m, uint32_t src, uint32_t dst) {
+    const std::vector<uint32_t> pair = {src, dst};
+    if (int rc = kv_move(m, pair, KV_MOVE_POOL)) return rc;
+    FH_CHECK_HIP(hipStreamSynchronize(m->stream));
+    return 0;
+}
+
+// blocks one staging pass of a swap carries (≥ 1), and the staging buffer grown to hold min(num_blocks, that many)
+static int kv_staging_for(FerrumHipModel* m, int num_blocks, int* per_pass) {
+    const size_t bb = kv_block_bytes(m->cfg);
+    *per_pass = (int)std::max<size_t>(1, KV_STAGING_CAP_BYTES / bb);
+    const size_t want = bb * (size_t)std::min(num_blocks, *per_pass);
+    if (m->kv_staging_bytes >= want) return 0;
+    FH_CHECK_HIP(hipStreamSynchronize(m->stream));
+    if (m->kv_staging) (void)hipFree(m->kv_staging);
+    m->kv_staging = nullptr;
+    m->kv_staging_bytes = 0;
+    FH_CHECK_HIP(hipMalloc((void**)&m->kv_staging, want));
+    m->kv_staging_bytes = want;
+    return 0;
+}
+
+int ferrum_hip_model_truncate_kv(FerrumHipModel* m, uint64_t seq_id, int new_len) {
+    FH_REQUIRE(m && m->finalized, "model_truncate_kv: model null or not finalized");
+    FH_REQUIRE(new_len >= 0, "model_truncate_kv: new_len=%d", new_len);
+    auto it = m->seqs.find(seq_id);
+    FH_REQUIRE(it != m->seqs.end(), "model_truncate_kv: unknown sequence %llu", (unsigned long long)seq_id);
+    SeqState& st = it->second;
+    if (new_len >= st.len) return 0;
+    const size_t keep = (size_t)cdiv(new_len, KV_BLOCK);
+    if (new_len % KV_BLOCK) {
+        // the block that becomes partial is the one the next forward writes into: another sequence's (fork, prefix hit) or the
+        // prefix cache's view of it must not change, so the sequence takes a private copy first
+        const size_t idx = (size_t)new_len / KV_BLOCK;
+        const uint32_t old = st.blocks[idx];
+        if (m->alloc->ref_count(old) > 1 || m->alloc->has_hash(old)) {
+            uint32_t fresh;
+            if (!m->alloc->allocate(&fresh)) {
+                fh::set_error("model_truncate_kv: sequence %llu shares block %u, which the cut at %d makes partial, and no block is free for "
+                              "a private copy", (unsigned long long)seq_id, old, new_len);
+                return FERRUM_HIP_INVALID;
+            }
+            if (int rc = kv_copy_block(m, old, fresh)) { m->alloc->free(&fresh, 1); return rc; }
+            st.blocks[idx] = fresh;
+            m->alloc->free(&old, 1);      // a hashed block stays a (soft-free) cache entry
+        }
+    }
+    if (st.blocks.size() > keep) {
+        m->alloc->free(st.blocks.data() + keep, (uint32_t)(st.blocks.size() - keep));
+        st.blocks.resize(keep);
+    }
+    st.len = new_len;
+    return 0;
+}
+
+int ferrum_hip_model_fork(FerrumHipModel* m, uint64_t src_seq_id, uint64_t dst_seq_id) {
+    FH_REQUIRE(m && m->finalized, "model_fork: model null or not finalized");
+    auto it = m->seqs.find(src_seq_id);
+    FH_REQUIRE(it != m->seqs.end() && it->second.len > 0, "model_fork: source sequence %llu is unknown or empty", (unsigned long long)src_seq_id);
+    FH_REQUIRE(m->seqs.find(dst_seq_id) == m->seqs.end(), "model_fork: destination sequence %llu exists", (unsigned long long)dst_seq_id);
+    const int len = it->second.len;
+    const size_t full = (size_t)len / KV_BLOCK;
+    // full blocks are shared; blocks the source reserved beyond its length are not inherited
+    std::vector<uint32_t> blocks(it->second.blocks.begin(), it->second.blocks.begin() + cdiv(len, KV_BLOCK));
+    for (size_t i = 0; i < full; i++)
+        FH_REQUIRE(m->alloc->ref_count(blocks[i]) < 0xFFFF, "model_fork: block %u is already shared 65535 times", blocks[i]);
+    if (len % KV_BLOCK) {       // the partial tail is where both sequences write next: the fork gets its own copy now
+        uint32_t fresh;
+        if (!m->alloc->allocate(&fresh)) {
+            fh::set_error("model_fork: no free block for the copy of the partial last block (kv length %d)", len);
+            return FERRUM_HIP_INVALID;
+        }
+        if (int rc = kv_copy_block(m, blocks[full], fresh)) { m->alloc->free(&fresh, 1); return rc; }
+        blocks[full] = fresh;
+    }
+    for (size_t i = 0; i < full; i++) m->alloc->acquire(blocks[i]);
+    SeqState& dst = m->seqs[dst_seq_id];
+    dst.blocks = std::move(blocks);
+    dst.len = len;
+    return 0;
+}
+
+int ferrum_hip_model_block_info(const FerrumHipModel* m, uint32_t block, uint32_t* ref_count, int* hashed) {
+    FH_REQUIRE(m && m->alloc, "model_block_info: null model");
+    FH_REQUIRE(block < m->alloc->capacity(), "model_block_info: block %u outside the pool of %u", block, m->alloc->capacity());
+    if (ref_count) *ref_count = m->alloc->ref_count(block);
+    if (hashed) *hashed = m->alloc->has_hash(block) ? 1 : 0;
+    return 0;
+}
+
+int ferrum_hip_model_kv_swap_bytes(const FerrumHipModel* m, uint64_t seq_id, size_t* bytes) {
+    FH_REQUIRE(m && m->finalized && bytes, "model_kv_swap_bytes: null argument or model not finalized");
+    auto it = m->seqs.find(seq_id);
+    FH_REQUIRE(it != m->seqs.end(), "model_kv_swap_bytes: unknown sequence %llu", (unsigned long long)seq_id);
+    *bytes = KV_SWAP_HEADER_BYTES + (size_t)cdiv(it->second.len, KV_BLOCK) * kv_block_bytes(m->cfg);
+    return 0;
+}
+
+int ferrum_hip_model_kv_swap_out(FerrumHipModel* m, uint64_t seq_id, void* host_buf, size_t capacity, size_t* written) {
+    FH_REQUIRE(m && m->finalized && host_buf && written, "model_kv_swap_out: null argument or model not finalized");
+    auto it = m->seqs.find(seq_id);
+    FH_REQUIRE(it != m->seqs.end(), "model_kv_swap_out: unknown sequence %llu", (unsigned long long)seq_id);
+    const FerrumHipModelConfig& c = m->cfg;
+    const SeqState& st = it->second;
+    const int nb = cdiv(st.len, KV_BLOCK);
+    const size_t bb = kv_block_bytes(c), need = KV_SWAP_HEADER_BYTES + (size_t)nb * bb;
+    FH_REQUIRE(capacity >= need, "model_kv_swap_out: sequence %llu needs %zu bytes, the buffer holds %zu", (unsigned long long)seq_id, need, capacity);
+    int per = 1;
+    if (int rc = kv_staging_for(m, nb, &per)) return rc;
+    const uint32_t header[8] = {KV_SWAP_MAGIC, KV_SWAP_VERSION, (uint32_t)c.num_layers, (uint32_t)c.num_kv_heads, (uint32_t)c.head_dim,
+                                (uint32_t)KV_BLOCK, (uint32_t)st.len, (uint32_t)nb};
+    static_assert(sizeof(header) == KV_SWAP_HEADER_BYTES, "swap header is 32 bytes");
+    memcpy(host_buf, header, sizeof(header));
+    uint8_t* payload = static_cast<uint8_t*>(host_buf) + KV_SWAP_HEADER_BYTES;
+    std::vector<uint32_t> pairs;
+    for (int b0 = 0; b0 < nb; b0 += per) {
+        const int n = std::min(per, nb - b0);
+        pairs.clear();
+        for (int i = 0; i < n; i++) { pairs.push_back(st.blocks[b0 + i]); pairs.push_back(0); }
+        if (int rc = kv_move(m, pairs, KV_MOVE_GATHER)) return rc;
+        FH_CHECK_HIP(hipMemcpyAsync(payload + (size_t)b0 * bb, m->kv_staging, (size_t)n * bb, hipMemcpyDeviceToHost, m->stream));
+        FH_CHECK_HIP(hipStreamSynchronize(m->stream));     // the staging buffer is reused by the next range
+    }
+    *written = need;
+    return ferrum_hip_model_release(m, seq_id);
+}
+
+int ferrum_hip_model_kv_swap_in(FerrumHipModel* m, uint64_t seq_id, const void* host_buf, size_t bytes) {
+    FH_REQUIRE(m && m->finalized && host_buf, "model_kv_swap_in: null argument or model not finalized");
+    FH_REQUIRE(bytes >= KV_SWAP_HEADER_BYTES, "model_kv_swap_in: %zu bytes hold no header", bytes);
+    const FerrumHipModelConfig& c = m->cfg;
+    uint32_t h[8];
+    memcpy(h, host_buf, sizeof(h));
+    FH_REQUIRE(h[0] == KV_SWAP_MAGIC && h[1] == KV_SWAP_VERSION, "model_kv_swap_in: not a KV swap buffer (magic %08x, version %u)", h[0], h[1]);
+    FH_REQUIRE(h[2] == (uint32_t)c.num_layers && h[3] == (uint32_t)c.num_kv_heads && h[4] == (uint32_t)c.head_dim && h[5] == (uint32_t)KV_BLOCK,
+               "model_kv_swap_in: buffer is of a model with %u layers, %u kv heads, head_dim %u, block %u; this one has %d, %d, %d, %d",
+               h[2], h[3], h[4], h[5], c.num_layers, c.num_kv_heads, c.head_dim, KV_BLOCK);
+    FH_REQUIRE(h[6] <= (uint32_t)c.max_seq_len && h[7] == (uint32_t)cdiv(h[6], KV_BLOCK) && (int)h[7] <= m->max_blocks_per_seq,
+               "model_kv_swap_in: kv length %u in %u blocks does not fit this model (max_seq_len %d)", h[6], h[7], c.max_seq_len);
+    const int len = (int)h[6], nb = (int)h[7];
+    const size_t bb = kv_block_bytes(c);
+    FH_REQUIRE(bytes == KV_SWAP_HEADER_BYTES + (size_t)nb * bb, "model_kv_swap_in: %zu bytes given, the header describes %zu", bytes,
+               KV_SWAP_HEADER_BYTES + (size_t)nb * bb);
+    FH_REQUIRE(m->seqs.find(seq_id) == m->seqs.end(), "model_kv_swap_in: sequence %llu exists", (unsigned long long)seq_id);
+    FH_REQUIRE((int)m->alloc->free_count() >= nb, "paged KV pool exhausted: swap-in needs %d blocks but only %u free", nb, m->alloc->free_count());
+    int per = 1;
+    if (int rc = kv_staging_for(m, nb, &per)) return rc;
+    std::vector<uint32_t> blocks((size_t)nb);
+    if (nb) m->alloc->allocate_n((uint32_t)nb, blocks.data());
+    const uint8_t* payload = static_cast<const uint8_t*>(host_buf) + KV_SWAP_HEADER_BYTES;
+    auto scatter = [&]() -> int {
+        std::vector<uint32_t> pairs;
+        for (int b0 = 0; b0 < nb; b0 += per) {
+            const int n = std::min(per, nb - b0);
+            pairs.clear();
+            for (int i = 0; i < n; i++) { pairs.push_back(0); pairs.push_back(blocks[b0 + i]); }
+            FH_CHECK_HIP(hipMemcpyAsync(m->kv_staging, payload + (size_t)b0 * bb, (size_t)n * bb, hipMemcpyHostToDevice, m->stream));
+            if (int rc = kv_move(m, pairs, KV_MOVE_SCATTER)) return rc;
+            FH_CHECK_HIP(hipStreamSynchronize(m->stream));
+        }
+        return 0;
+    };
+    if (int rc = scatter()) { m->alloc->free(blocks.data(), (uint32_t)nb); return rc; }
+    SeqState& st = m->seqs[seq_id];
+    st.blocks = std::move(blocks);
+    st.len = len;
+    return 0;
 }
 
 int ferrum_hip_model_enable_taps(FerrumHipModel* m, int enable) {

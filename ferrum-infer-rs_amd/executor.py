@@ -333,6 +333,39 @@ class HipModel:
                                                      out.ctypes.data_as(C.POINTER(C.c_float))), "read_kv")
         return out
 
+    # ── sequence KV lifecycle (roll-back, fork, host swap) ───────────────────
+    def truncate_kv(self, seq_id, new_len):
+        """DecoderOnlyLLM::truncate_kv (common/llm.rs:286): cut the sequence back to new_len tokens (≥ its length: no-op)."""
+        _check(self.lib.ferrum_hip_model_truncate_kv(self.h, C.c_uint64(seq_id), int(new_len)), "truncate_kv")
+
+    def fork(self, src_seq_id, dst_seq_id):
+        """dst shares src's full blocks (ref counts) and gets a copy of its partial last block."""
+        _check(self.lib.ferrum_hip_model_fork(self.h, C.c_uint64(src_seq_id), C.c_uint64(dst_seq_id)), "fork")
+
+    def swap_bytes(self, seq_id):
+        n = C.c_size_t()
+        _check(self.lib.ferrum_hip_model_kv_swap_bytes(self.h, C.c_uint64(seq_id), C.byref(n)), "kv_swap_bytes")
+        return int(n.value)
+
+    def swap_out(self, seq_id, capacity=None):
+        """Copy the sequence's KV to the host and release it; returns the swap buffer as `bytes` (header + blocks)."""
+        cap = self.swap_bytes(seq_id) if capacity is None else int(capacity)
+        buf = (C.c_uint8 * max(cap, 1))()
+        written = C.c_size_t()
+        _check(self.lib.ferrum_hip_model_kv_swap_out(self.h, C.c_uint64(seq_id), buf, C.c_size_t(cap), C.byref(written)), "kv_swap_out")
+        return bytes(memoryview(buf)[:written.value])
+
+    def swap_in(self, seq_id, data):
+        """Bring a swapped-out sequence back under seq_id (fresh, private block ids)."""
+        data = bytes(data)
+        _check(self.lib.ferrum_hip_model_kv_swap_in(self.h, C.c_uint64(seq_id), data, C.c_size_t(len(data))), "kv_swap_in")
+
+    def block_info(self, block):
+        """(ref count, carries a prefix-cache hash) of one physical block of the pool."""
+        rc, hashed = C.c_uint32(), C.c_int()
+        _check(self.lib.ferrum_hip_model_block_info(self.h, C.c_uint32(block), C.byref(rc), C.byref(hashed)), "block_info")
+        return int(rc.value), bool(hashed.value)
+
     # ── forward ──────────────────────────────────────────────────────────────
     def unified_forward(self, items, greedy=True, want_logits=False, token_mask=None, repetition_penalties=None):
         """items: [(seq_id, tokens, pos_offset, is_final_chunk)].  Returns (tokens|None, logits|None) for the

@@ -259,6 +259,14 @@ int ferrum_hip_paged_decode_attention_fused_qkv_f16(const void* qkv, const void*
 int ferrum_hip_paged_kv_read_f16(const void* cache_k, const void* cache_v, const int32_t* block_table, int kv_len,
                                  int kv_heads, int head_dim, int block_size, void* k_out, void* v_out,
                                  void* stream);
+/* Whole-block moves over any number of pools in ONE launch — the kernel behind ferrum_hip_model_fork / _truncate_kv / _kv_swap_*.
+ * pools_dev: DEVICE array of num_pools pool base pointers, every pool [num_blocks][chunk_bytes] (chunk_bytes = kv_heads·16·head_dim·2,
+ * a multiple of 16); pairs_dev: DEVICE array of num_pairs (src_block, dst_block) u32 pairs.  mode 0 pool → pool (dst = src inside
+ * every pool), 1 gather (staging_dev[pair][pool][chunk] = pool[pair.src]; .dst ignored), 2 scatter (pool[pair.dst] =
+ * staging_dev[pair][pool][chunk]; .src ignored).  staging_dev is 16-byte aligned (unused in mode 0).  A pair that names a block
+ * id ≥ num_blocks moves nothing. */
+int ferrum_hip_kv_move_blocks(const void* const* pools_dev, int num_pools, const uint32_t* pairs_dev, int num_pairs, void* staging_dev,
+                              size_t chunk_bytes, int num_blocks, int mode, void* stream);
 
 /* ── MoE routing: BackendMoeFused (capabilities.rs:305-724) ─────────────────────────────────────
  * route_topk_softmax (:334; CPU ferrum-models/src/moe/router.rs:113-195), moe_align_block_size_pair_ids
@@ -539,6 +547,39 @@ int ferrum_hip_model_block_table(const FerrumHipModel* model, uint64_t seq_id, u
                                  int* num_blocks, int* kv_len);
 /* Read a sequence's K or V of one layer back as fp32 [kv_len, kv_heads, head_dim]. */
 int ferrum_hip_model_read_kv_f32(FerrumHipModel* model, uint64_t seq_id, int layer, int is_v, float* out_host);
+
+/* ── sequence KV lifecycle: roll-back, copy-on-write fork, host swap.  DecoderOnlyLLM::truncate_kv (ferrum-models/src/common/
+ *    llm.rs:286; llama_family.rs:5021) / ModelExecutor::truncate_kv; the swap pair is what the reference's KV manager only
+ *    stubs (ferrum-kv/src/managers/paged.rs:623,652,718).  All five are host-synchronous on the model stream, like release and
+ *    read_kv_f32, move whole 16-token blocks of every layer in one launch each (csrc/kv_move.hip) and are never part of the
+ *    captured decode step (block tables are uploaded on every decode_steps call).  A failure returns FERRUM_HIP_INVALID with
+ *    ferrum_hip_last_error set and leaves the model exactly as it was.  Tensor parallel: every rank holds its own KV shard, so
+ *    the calls are rank-local — issue the same call on every rank; nothing goes through the communicator. ── */
+/* Cut a sequence back to new_len tokens; the next forward continues at pos_offset = new_len.  new_len ≥ the current length is a
+ * no-op (as in the reference); an unknown sequence is an error.  Blocks wholly beyond ceil(new_len / 16) go back to the
+ * allocator — UNLIKE the reference, which keeps them reserved; the next forward reserves on demand, and a block that carries a
+ * prefix-cache hash stays a valid soft-free cache entry.  When the cut falls inside a block that another sequence shares
+ * (fork, prefix hit) or that is a prefix-cache entry, the sequence first takes a private copy of that block, because its next
+ * write lands there; that needs one free block, else INVALID. */
+int ferrum_hip_model_truncate_kv(FerrumHipModel* model, uint64_t seq_id, int new_len);
+/* dst becomes a second owner of src's context (parallel sampling, beams): dst must not exist, src must hold ≥ 1 token.  Full
+ * blocks are shared through their ref counts (a block already shared 65535 times → INVALID); a partial last block is copied
+ * into a fresh block right away (one free block needed when len % 16 != 0, else INVALID), so no write of either sequence can
+ * reach the other.  Blocks src reserved beyond its length are not inherited.  dst's length = src's. */
+int ferrum_hip_model_fork(FerrumHipModel* model, uint64_t src_seq_id, uint64_t dst_seq_id);
+/* Preemption without re-prefill.  swap_out copies the ceil(len / 16) used blocks of every layer to host_buf and then releases
+ * the sequence exactly as ferrum_hip_model_release does; swap_in brings it back under seq_id (which must not exist) on whatever
+ * block ids the allocator hands out — all private, none hashed — and restores its length.  Buffer: a 32-byte header of eight
+ * little-endian u32 {magic "FHKV", version 1, num_layers, num_kv_heads, head_dim, block size 16, kv_len, num_blocks}, then the
+ * payload [block][layer][K, V][kv_heads·16·head_dim fp16] in the native tile layout (csrc/kv_layout.h); slots at and beyond
+ * kv_len are don't-care.  swap_bytes reports the size swap_out needs; a smaller capacity fails before anything moves.  swap_in
+ * checks the header against this model's dimensions and the byte count; an exhausted pool → INVALID, nothing taken. */
+int ferrum_hip_model_kv_swap_bytes(const FerrumHipModel* model, uint64_t seq_id, size_t* bytes);
+int ferrum_hip_model_kv_swap_out(FerrumHipModel* model, uint64_t seq_id, void* host_buf, size_t capacity, size_t* written);
+int ferrum_hip_model_kv_swap_in(FerrumHipModel* model, uint64_t seq_id, const void* host_buf, size_t bytes);
+/* Sharing state of one physical block of the model's pool: its ref count (0 = free or soft-free) and whether it carries a
+ * prefix-cache hash.  Either output may be NULL.  For tests and for schedulers that price a fork or a truncate. */
+int ferrum_hip_model_block_info(const FerrumHipModel* model, uint32_t block, uint32_t* ref_count, int* hashed);
 
 /* ModelExecutor::unified_decode (model_executor.rs; llm.rs:260): mixed prefill+decode forward.
  * For every item with is_final_chunk, in item order:
