@@ -222,19 +222,54 @@ int ferrum_hip_embedding_lookup_f16(const void* table, const uint32_t* ids, void
     return embedding_lookup_f16(CH(table), ids, H(out), n_ids, dim, ST(stream));
 }
 int ferrum_hip_fused_silu_mul_split_f16(const void* gate_up, void* out, int tokens, int im, void* stream) {
+    FH_REQUIRE(tokens == 0 || (gate_up && out), "fused_silu_mul_split: null buffer");
     return fused_silu_mul_split_f16(CH(gate_up), H(out), tokens, im, ST(stream));
 }
 int ferrum_hip_fused_gelu_tanh_mul_split_f16(const void* gate_up, void* out, int tokens, int im, void* stream) {
+    FH_REQUIRE(tokens == 0 || (gate_up && out), "fused_gelu_tanh_mul_split: null buffer");
     return fused_gelu_tanh_mul_split_f16(CH(gate_up), H(out), tokens, im, ST(stream));
 }
 int ferrum_hip_scale_inplace_f16(void* buf, float scale, size_t len, void* stream) {
+    FH_REQUIRE(len == 0 || buf, "scale_inplace: null buffer");
     return scale_inplace_f16(H(buf), scale, (long)len, ST(stream));
 }
 int ferrum_hip_add_inplace_f16(void* residual, const void* x, size_t len, void* stream) {
+    FH_REQUIRE(len == 0 || (residual && x), "add_inplace: null buffer");
     return add_inplace_f16(H(residual), CH(x), (long)len, ST(stream));
 }
 int ferrum_hip_add_bias_f16(void* data, const void* bias, int rows, int cols, void* stream) {
+    FH_REQUIRE(rows == 0 || cols == 0 || (data && bias), "add_bias: null buffer");
     return add_bias_f16(H(data), CH(bias), rows, cols, ST(stream));
+}
+
+// ── head / tail of a forward, slab-input and gathered-store forms (the runner's own launches, exported op by op) ──
+int ferrum_hip_fused_add_rms_norm_perm_f16(void* residual, const void* x, const void* w, float eps, void* out, int tokens, int dim,
+                                           const int32_t* out_perm, void* stream) {
+    FH_REQUIRE(tokens == 0 || (residual && x && w && out), "fused_add_rms_norm_perm: null buffer");
+    return fused_add_rms_norm_f16(H(residual), CH(x), CH(w), eps, H(out), tokens, dim, ST(stream), out_perm);
+}
+int ferrum_hip_embed_rms_norm_f16(const void* table, const uint32_t* token_ids, float embed_scale, void* residual, float* residual_f32,
+                                  const void* w, float eps, void* norm_out, int tokens, int dim, unsigned* zero_words, int n_zero,
+                                  const int32_t* out_perm, void* stream) {
+    FH_REQUIRE(tokens == 0 || (table && token_ids && w && norm_out), "embed_rms_norm: null buffer");
+    FH_REQUIRE(n_zero >= 0 && (n_zero == 0 || zero_words), "embed_rms_norm: n_zero=%d without zero_words", n_zero);
+    return embed_rms_norm_f16(CH(table), token_ids, embed_scale, H(residual), residual_f32, CH(w), eps, H(norm_out), tokens, dim,
+                              zero_words, n_zero, ST(stream), out_perm);
+}
+int ferrum_hip_gather_rms_norm_f16(const void* x, const int32_t* row_idx, const void* w, float eps, void* out, int rows, int dim,
+                                   void* stream) {
+    FH_REQUIRE(rows == 0 || (x && row_idx && w && out), "gather_rms_norm: null buffer");
+    return gather_rms_norm_f16(CH(x), row_idx, CH(w), eps, H(out), rows, dim, ST(stream));
+}
+int ferrum_hip_fused_gated_act_slabs_f16(const float* slabs, int num_slabs, size_t slab_stride, int ld, void* out, int tokens, int im,
+                                         int gelu, void* stream) {
+    FH_REQUIRE(tokens == 0 || (slabs && out), "fused_gated_act_slabs: null buffer");
+    return fused_gated_act_slabs_f16(slabs, num_slabs, (long)slab_stride, ld, H(out), tokens, im, gelu, ST(stream));
+}
+int ferrum_hip_gather_columns_f16(const void* in, const int32_t* perm, void* out, int rows, int cols, void* stream) {
+    FH_REQUIRE(rows == 0 || cols == 0 || (in && perm && out), "gather_columns: null buffer");
+    FH_REQUIRE(in != out || rows == 0, "gather_columns: in place");
+    return gather_columns_f16(CH(in), perm, H(out), rows, cols, ST(stream));
 }
 
 int ferrum_hip_layer_norm_f16(const void* x, const void* gamma, const void* beta, float eps, void* out, int tokens, int dim, void* stream) {
@@ -567,6 +602,20 @@ int ferrum_hip_sandwich_add_rms_norm_f32(const void* branch_f16, const void* w_b
     FH_REQUIRE(tokens == 0 || (branch_f16 && w_branch && residual_f32 && (!w_next || norm_out_f16)), "sandwich_add_rms_norm_f32: null buffer");
     return sandwich_add_rms_norm_f32(CH(branch_f16), CH(w_branch), residual_f32, CH(w_next), eps, H(norm_out_f16), tokens, dim,
                                      ST(stream));
+}
+int ferrum_hip_sandwich_add_rms_norm_f32_perm(const void* branch_f16, const void* w_branch, float* residual_f32, const void* w_next,
+                                              float eps, void* norm_out_f16, int tokens, int dim, const int32_t* out_perm, void* stream) {
+    FH_REQUIRE(tokens == 0 || (branch_f16 && w_branch && residual_f32 && (!w_next || norm_out_f16)), "sandwich_add_rms_norm_f32_perm: null buffer");
+    return sandwich_add_rms_norm_f32(CH(branch_f16), CH(w_branch), residual_f32, CH(w_next), eps, H(norm_out_f16), tokens, dim,
+                                     ST(stream), out_perm);
+}
+int ferrum_hip_sandwich_add_rms_norm_f32_slabs(const float* slabs, int num_slabs, size_t slab_stride, int ld_slab, const void* w_branch,
+                                               float* residual_f32, const void* w_next, float eps, void* norm_out_f16, int tokens,
+                                               int dim, const int32_t* out_perm, void* stream) {
+    FH_REQUIRE(tokens == 0 || (slabs && w_branch && residual_f32 && (!w_next || norm_out_f16)), "sandwich_add_rms_norm_f32_slabs: null buffer");
+    FH_REQUIRE(ld_slab >= dim, "sandwich_add_rms_norm_f32_slabs: ld_slab=%d < dim=%d", ld_slab, dim);
+    return sandwich_add_rms_norm_f32_slabs(slabs, num_slabs, (long)slab_stride, ld_slab, CH(w_branch), residual_f32, CH(w_next), eps,
+                                           H(norm_out_f16), tokens, dim, ST(stream), out_perm);
 }
 int ferrum_hip_rms_norm_f32_to_f16(const float* x_f32, const int32_t* row_idx, const void* w, float eps, void* out_f16, int n_rows,
                                    int dim, void* stream) {

@@ -83,6 +83,28 @@ int ferrum_hip_fused_gelu_tanh_mul_split_f16(const void* gate_up, void* out, int
 int ferrum_hip_scale_inplace_f16(void* buf, float scale, size_t len, void* stream);
 int ferrum_hip_add_inplace_f16(void* residual, const void* x, size_t len, void* stream);
 int ferrum_hip_add_bias_f16(void* data, const void* bias, int rows, int cols, void* stream);
+/* The forms the model runner launches around those ops, one entry point each (no new arithmetic: the launchers the
+ * runner calls).  out_perm (NULL = none; else `dim` int32 column indices, a permutation): the norm output is stored
+ * gathered, out[row][j] = y[row][out_perm[j]], for an act-order consumer.
+ *   fused_add_rms_norm_perm   ferrum_hip_fused_add_rms_norm_f16 with out_perm.
+ *   embed_rms_norm            embedding_lookup → scale (embed_scale 0 = none; fp16 rounding, like scale_inplace) →
+ *                             copies of the scaled row (residual fp16 and / or residual_f32, NULL = skipped) → rms_norm·w.
+ *                             The launch also zeroes zero_words[0 .. n_zero) (NULL / 0 = none).  dim % 8 == 0, ≤ 16384.
+ *   gather_rms_norm           out[i] = rms_norm(x[row_idx[i]])·w (final norm of the sampled rows).
+ *   fused_gated_act_slabs     fused_{silu,gelu_tanh}_mul_split on a gate_up that arrives as num_slabs fp32 split-K slabs
+ *                             [num_slabs][slab_stride] of rows [tokens][ld ≥ 2·intermediate]: summed in slab order,
+ *                             rounded to fp16 once, then the activation — bit-identical to reduce → fused_*_mul_split.
+ *   gather_columns            out[r][j] = in[r][perm[j]] (kernels/gather_columns.cu:15); not in place. */
+int ferrum_hip_fused_add_rms_norm_perm_f16(void* residual, const void* x, const void* w, float eps, void* out, int tokens, int dim,
+                                           const int32_t* out_perm, void* stream);
+int ferrum_hip_embed_rms_norm_f16(const void* table, const uint32_t* token_ids_dev, float embed_scale, void* residual,
+                                  float* residual_f32, const void* w, float eps, void* norm_out, int tokens, int dim,
+                                  unsigned* zero_words, int n_zero, const int32_t* out_perm, void* stream);
+int ferrum_hip_gather_rms_norm_f16(const void* x, const int32_t* row_idx, const void* w, float eps, void* out, int rows, int dim,
+                                   void* stream);
+int ferrum_hip_fused_gated_act_slabs_f16(const float* slabs, int num_slabs, size_t slab_stride, int ld, void* out, int tokens,
+                                         int intermediate, int gelu, void* stream);
+int ferrum_hip_gather_columns_f16(const void* in, const int32_t* perm, void* out, int rows, int cols, void* stream);
 /* Backend::layer_norm / Backend::gelu (traits.rs, required core ops; CPU cpu.rs:2081-2122 — exact-form GELU with the
  * reference's own erf polynomial, cpu.rs:2263-2273).  Not on the LLM decode path; present so that the binding returns
  * "unsupported" for no required method. */
@@ -185,6 +207,14 @@ int ferrum_hip_moe_pair_status(const FerrumHipGptq* gate_up_stack, unsigned* tim
 int ferrum_hip_sandwich_add_rms_norm_f32(const void* branch_f16, const void* w_branch, float* residual_f32,
                                          const void* w_next, float eps, void* norm_out_f16, int tokens, int dim, void* stream);
 /* out_f16[i] = rms_norm(residual_f32[row_idx ? row_idx[i] : i], w) — final norm / first input norm of the fp32 stream */
+/* The same with the norm output stored gathered (out_perm as above), and with the branch arriving as num_slabs fp32
+ * split-K slabs [num_slabs][slab_stride] of rows [tokens][ld_slab ≥ dim]: branch = fp16(Σ slabs in slab order).  dim % 8 == 0, ≤ 8192. */
+int ferrum_hip_sandwich_add_rms_norm_f32_perm(const void* branch_f16, const void* w_branch, float* residual_f32,
+                                              const void* w_next, float eps, void* norm_out_f16, int tokens, int dim,
+                                              const int32_t* out_perm, void* stream);
+int ferrum_hip_sandwich_add_rms_norm_f32_slabs(const float* slabs, int num_slabs, size_t slab_stride, int ld_slab,
+                                               const void* w_branch, float* residual_f32, const void* w_next, float eps,
+                                               void* norm_out_f16, int tokens, int dim, const int32_t* out_perm, void* stream);
 int ferrum_hip_rms_norm_f32_to_f16(const float* x_f32, const int32_t* row_idx, const void* w, float eps, void* out_f16,
                                    int n_rows, int dim, void* stream);
 

@@ -15,6 +15,9 @@ tolerance that is derived from the number formats, not measured on the code unde
   * 2^-24             the smallest fp16 subnormal: the floor below which the format cannot resolve.
 
 A bias is one more term of the sum (x = 1, w = bias): callers add it to `ref64` and |bias| to `absdot64`.
+
+The row norms, the fp32 residual stream's sandwich update, the gated activations and layer_norm have bounds of their own
+further down ("norm family"), derived the same way; each function's docstring carries its derivation.
 """
 import numpy as np
 
@@ -153,3 +156,218 @@ def emulate_layer0_kv(embed_rows, input_ln, w_qkv, k_norm, positions, nq, nkv, h
     k0, k1 = k[..., :half], k[..., half:]
     kr = np.concatenate([k0 * c - k1 * s, k1 * c + k0 * s], axis=-1)
     return f16r(kr), f16r(v)                                                                           # fp16: the cache
+
+
+# ── norm family (csrc/norm.hip): row norms, sandwich update, gated activations, layer_norm ──────────────────────────────
+EPS_F32 = 2.0 ** -24          # unit roundoff of fp32
+FLOOR_F32 = 2.0 ** -149       # smallest fp32 subnormal
+ROW_KINDS = ("normal", "first", "last", "big", "subnormal", "zero", "v255", "v256")
+
+
+def mixed_sign_weight(rng, dim):
+    """fp16 norm weight 1 + 0.3·N(0, 1) with a quarter of the signs flipped."""
+    return f16r((1.0 + 0.3 * rng.standard_normal(dim)) * np.where(rng.random(dim) < 0.25, -1.0, 1.0))
+
+
+def norm_rows(rng, rows, dim, start=0):
+    """fp16-valued [rows, dim] test rows, kind of row i = ROW_KINDS[(start + i) % 8]:
+      normal     N(0, 1);
+      first / last / v255 / v256
+                 N(0, 1) with ONE 8-element vector at ±30·(1 ± 5 %): about half of the row's energy at dim 8192, nearly
+                 all of it at small dims.  A row sum that drops, repeats or adds such a vector moves the norm scale by
+                 tens of per cent, where the same fault on a normal row (8 of dim terms) hides inside the any-order
+                 allowance.  Vector 0, the last one, and the two vectors either side of the first 256-thread chunk seam
+                 (v255 / v256 fall back to the last vector where dim has no such vector);
+      big        |x| in [5e4, 6e4]: squares of 3.6e9, the fp16 range's end;
+      subnormal  fp16 subnormals k·2^-24, k in [1, 1023]: eps decides the scale;
+      zero       all zero: the output is 0 (eps > 0), never NaN.
+    Returns (x, kinds)."""
+    nvec = dim // 8
+    x = rng.standard_normal((rows, dim))
+    kinds = [ROW_KINDS[(start + i) % len(ROW_KINDS)] for i in range(rows)]
+    for i, kind in enumerate(kinds):
+        if kind in ("first", "last", "v255", "v256"):
+            v = {"first": 0, "last": nvec - 1, "v255": 255, "v256": 256}[kind]
+            v = v if v < nvec else nvec - 1
+            x[i, v * 8:v * 8 + 8] = 30.0 * (1.0 + 0.05 * rng.standard_normal(8)) * rng.choice([-1.0, 1.0], 8)
+        elif kind == "big":
+            x[i] = rng.uniform(5e4, 6e4, dim) * rng.choice([-1.0, 1.0], dim)
+        elif kind == "subnormal":
+            x[i] = rng.integers(1, 1024, dim) * 2.0 ** -24 * rng.choice([-1.0, 1.0], dim)
+        elif kind == "zero":
+            x[i] = 0.0
+    return f16r(x), kinds
+
+
+def rms_norm_ref64(x, w, eps):
+    """(x·inv·w, inv) in float64, inv = 1/sqrt(mean(x²) + eps) per row; eps is the float32 the kernel receives."""
+    x64 = np.asarray(x, np.float64)
+    inv = 1.0 / np.sqrt((x64 * x64).mean(axis=-1, keepdims=True) + float(np.float32(eps)))
+    return x64 * inv * np.asarray(w, np.float64), inv
+
+
+def norm_scale_allowance(dim):
+    """Relative error of x·inv·w held in fp32, before any store: dim·2^-25 + 8·2^-24.
+
+    The row sum: each square rounds once when x is fp32 (exact for fp16 x), and a sum of dim non-negative terms in ANY
+    order is within (dim − 1)·2^-24 relative — dim·2^-24 with the squares' own rounding.  /dim and +eps round once each
+    (both terms non-negative, so relative errors do not grow): (dim + 2)·2^-24 on the argument of the square root, which
+    halves it: dim·2^-25 + 2^-24 on inv, plus a correctly rounded sqrt and divide (2^-24 each; 2.5 ulp covers a fast
+    divide) and the two multiplies x·inv and ·w (2^-24 each): dim·2^-25 + (1 + 1 + 2.5 + 2)·2^-24 ≤ dim·2^-25 + 8·2^-24.
+    The kernel's tree order is not modelled: any order is allowed."""
+    return dim * 2.0 ** -25 + 8 * EPS_F32
+
+
+def rms_norm_tolerance(ref64, dim):
+    """|got − ref| ≤ |ref|·(2^-11 + dim·2^-25 + 8·2^-24) + 2^-24: one fp16 rounding of the stored result on top of
+    norm_scale_allowance, and the fp16 floor (a subnormal result rounds by at most 2^-25)."""
+    return np.abs(np.asarray(ref64, np.float64)) * (EPS_F16 + norm_scale_allowance(dim)) + FLOOR_F16
+
+
+def assert_rms_norm_elementwise(x, w, eps, got, what="rms_norm"):
+    """Every element of got = fp16(x·inv·w) against float64 from the rows `x` (fp16- or fp32-valued) the kernel normed."""
+    ref, _ = rms_norm_ref64(x, w, eps)
+    return assert_within(ref, rms_norm_tolerance(ref, np.asarray(x).shape[-1]), got, what)
+
+
+def assert_sandwich_residual(branch, w_branch, residual_in, eps, got, what="sandwich residual"):
+    """residual_out = residual_in + b in fp32, b = rms_norm(branch)·w_branch never stored:
+
+        |got − (r + b)| ≤ 2^-24·|r + b| + |b|·(dim·2^-25 + 8·2^-24) + 2^-149
+
+    b carries norm_scale_allowance; the add rounds once (2^-24 of the result; 2^-149 where the result is subnormal)."""
+    b, _ = rms_norm_ref64(branch, w_branch, eps)
+    ref = np.asarray(residual_in, np.float64) + b
+    tol = EPS_F32 * np.abs(ref) + np.abs(b) * norm_scale_allowance(np.asarray(branch).shape[-1]) + FLOOR_F32
+    return assert_within(ref, tol, got, what)
+
+
+def slabs_to_f16(slabs):
+    """fp16(Σ_s slab_s) exactly as the device forms it: float32 adds in slab order from 0, one fp16 rounding.  [S, …] → […]."""
+    slabs = np.asarray(slabs, np.float32)
+    acc = np.zeros(slabs.shape[1:], np.float32)
+    for s in range(slabs.shape[0]):
+        acc = acc + slabs[s]
+    with np.errstate(over="ignore"):
+        return acc.astype(np.float16).astype(np.float32)
+
+
+def split_into_slabs(rng, target, S):
+    """S float32 slabs whose slab-order sum is `target` up to fp32 rounding (an all-zero row stays exactly zero): S − 1
+    random slabs of half the row's largest magnitude and the remainder."""
+    t = np.asarray(target, np.float32)
+    scale = (0.5 * np.abs(t).max(axis=-1, keepdims=True)).astype(np.float32)
+    out = np.empty((S,) + t.shape, np.float32)
+    acc = np.zeros_like(t)
+    for s in range(S - 1):
+        out[s] = rng.standard_normal(t.shape).astype(np.float32) * scale
+        acc = acc + out[s]
+    out[S - 1] = t - acc
+    return out
+
+
+GATE_PLANTS = (12.0, -12.0, 30.0, -30.0, 65504.0, -65504.0)
+
+
+def gated_inputs(rng, rows, im):
+    """fp16-valued gate_up [rows, 2·im] (gate columns, then up columns): 3·N(0, 1), with the six gates of GATE_PLANTS
+    planted evenly through the tensor.  Under a ±65504 gate the up value is divided by 16 and clipped to ±0.9, so that the
+    product stays a finite fp16."""
+    gu = 3.0 * rng.standard_normal((rows, 2 * im))
+    g, u = gu[:, :im], gu[:, im:]
+    pos = np.linspace(0, rows * im - 1, len(GATE_PLANTS)).astype(int)
+    for p, v in zip(pos, GATE_PLANTS):
+        r, c = divmod(int(p), im)
+        g[r, c] = v
+        if abs(v) > 1e4:
+            u[r, c] = np.clip(u[r, c] / 16.0, -0.9, 0.9)
+    return f16r(gu)
+
+
+def silu_mul_ref64(g, u):
+    g, u = np.asarray(g, np.float64), np.asarray(u, np.float64)
+    with np.errstate(over="ignore"):
+        return g / (1.0 + np.exp(-g)) * u
+
+
+GELU_C0, GELU_C1 = float(np.float32(0.79788456)), float(np.float32(0.044715))     # the constants of the op, as fp32 holds them
+
+
+def gelu_tanh_mul_ref64(g, u):
+    g, u = np.asarray(g, np.float64), np.asarray(u, np.float64)
+    return 0.5 * g * (1.0 + np.tanh(GELU_C0 * (g + GELU_C1 * g * g * g))) * u
+
+
+def silu_mul_tolerance(ref64):
+    """out = fp16(g/(1 + exp(−g))·u) from fp16 g, u in fp32:  |got − ref| ≤ |ref|·(2^-11 + 2^-17) + 2^-24.
+
+    fp32 part: the fast exp scales its argument by log2(e) before exp2 and so loses |g|·2^-24 relative besides its own
+    ~2 ulp; 1 + e, the divide (≤ 2.5 ulp) and ·u round once each: (|g| + 6.5)·2^-24 ≤ 2^-17 for |g| ≤ 120.  Past |g| ≈ 32
+    nothing of it is visible: for g < −32, |silu(g)·u| < 32·e^-32·65504 < 2^-24, under the floor; for g > 32, e^-g < 2^-46
+    and silu(g) = g to fp32 precision whatever exp returns (0 and inf included: g/(1 + 0) = g, g/inf = 0)."""
+    return np.abs(np.asarray(ref64, np.float64)) * (EPS_F16 + 2.0 ** -17) + FLOOR_F16
+
+
+def gelu_tanh_mul_tolerance(ref64, g, u=1.0):
+    """out = fp16(0.5·g·(1 + tanh(inner))·u), inner = c0·(g + c1·g³), in fp32:
+
+        |got − ref| ≤ |ref|·(2^-11 + 2^-17) + |g|·|u|·2^-22 + 2^-24
+
+    The bracket 1 + t cancels for negative g (t → −1), so its error is absolute, not relative: tanhf is good to ~2 ulp of
+    |t| ≤ 1 (2·2^-24); inner carries 4 roundings, which move t by 4·2^-24·|inner|·(1 − t²) ≤ 4·2^-24·0.45 (x·sech²x ≤ 0.448);
+    the sum 1 + t rounds by 2^-24·(1 + t) ≤ 2·2^-24: under 6·2^-24 in all, allowed 8·2^-24 = 2^-21.  Times 0.5·|g|·|u|, that is
+    |g|·|u|·2^-22.  At g = −4 (1 + t = 3.5e-5 ≈ 2^-15) an absolute 2^-24 alone is 2^-9 of the result: about three fp16
+    ulps, which a purely relative bound would reject.  The remaining multiplies are relative (2^-17 covers them).
+    With u = 1 the same bound serves the erf-form `gelu` op, whose bracket 1 − (1 − p·exp(−z²)) cancels the same way."""
+    g, u = np.asarray(g, np.float64), np.asarray(u, np.float64)
+    return np.abs(np.asarray(ref64, np.float64)) * (EPS_F16 + 2.0 ** -17) + np.abs(g) * np.abs(u) * 2.0 ** -22 + FLOOR_F16
+
+
+def assert_gated_act_elementwise(gate_up, got, gelu, what=None):
+    """fused_{silu,gelu_tanh}_mul_split of an fp16-valued gate_up [rows, 2·im] against float64, every element."""
+    gate_up = np.asarray(gate_up, np.float64)
+    im = gate_up.shape[1] // 2
+    g, u = gate_up[:, :im], gate_up[:, im:]
+    if gelu:
+        ref = gelu_tanh_mul_ref64(g, u)
+        return assert_within(ref, gelu_tanh_mul_tolerance(ref, g, u), got, what or "gelu_tanh·mul")
+    ref = silu_mul_ref64(g, u)
+    return assert_within(ref, silu_mul_tolerance(ref), got, what or "silu·mul")
+
+
+def gelu_erf_poly_ref64(x):
+    """The `gelu` op's own function in float64: 0.5·x·(1 + erf(x/√2)) with the Abramowitz–Stegun 7.1.26 polynomial (fp32
+    coefficients) that the op defines as its erf."""
+    x = np.asarray(x, np.float64)
+    z = x / np.sqrt(2.0)
+    az = np.abs(z)
+    c = [float(np.float32(v)) for v in (0.3275911, 1.0614054, 1.4531521, 1.4214138, 0.28449672, 0.2548296)]
+    t = 1.0 / (1.0 + c[0] * az)
+    y = 1.0 - (((((c[1] * t - c[2]) * t) + c[3]) * t - c[4]) * t + c[5]) * t * np.exp(-az * az)
+    return 0.5 * x * (1.0 + np.where(z < 0, -1.0, 1.0) * y)
+
+
+def layer_norm_ref_tol(x, gamma, beta, eps):
+    """out = fp16((x − mean)·inv·γ + β), inv = 1/sqrt(mean((x − mean)²) + eps), two passes in fp32 → (ref64, tol64):
+
+        tol = 2^-11·|ref| + |n|·(dim·2^-25 + 8·2^-24) + M·inv·|γ| + 2^-24·|ref| + 2^-24,   n = (x − mean)·inv·γ,
+        M   = dim·2^-24·max|x − mean|   (the cancellation term: the absolute error of the fp32 mean)
+
+    The mean is an fp32 sum of dim signed terms in any order: |δmean| ≤ dim·2^-24·mean|x|.  The term is stated with
+    max|x − mean| of the row, which is no smaller on rows whose spread exceeds their offset — asserted here, so the
+    bound is only used where it is derived.  Every d = x − mean carries that SAME shift δmean (plus its own 2^-24), so
+    n is off by M·inv·|γ| absolutely — the cancellation — while the variance does not see the shift to first order
+    (Σd = 0: Σ(d + δ)² = Σd² + dim·δ²) and inv carries the row norm's allowance.  The β add rounds once (2^-24·|ref|),
+    then the fp16 store."""
+    x64 = np.asarray(x, np.float64)
+    dim = x64.shape[-1]
+    mean = x64.mean(axis=-1, keepdims=True)
+    d = x64 - mean
+    assert np.all(np.abs(x64).mean(axis=-1) <= np.abs(d).max(axis=-1)), "row offset exceeds its spread: M understates the mean's error"
+    inv = 1.0 / np.sqrt((d * d).mean(axis=-1, keepdims=True) + float(np.float32(eps)))
+    gam = np.asarray(gamma, np.float64)
+    n = d * inv * gam
+    ref = n + np.asarray(beta, np.float64)
+    M = dim * EPS_F32 * np.abs(d).max(axis=-1, keepdims=True)
+    tol = (EPS_F16 + EPS_F32) * np.abs(ref) + np.abs(n) * norm_scale_allowance(dim) + M * inv * np.abs(gam) + FLOOR_F16
+    return ref, tol

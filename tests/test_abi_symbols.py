@@ -336,3 +336,39 @@ def test_rust_crate_implements_every_required_trait_method():
             assert count in fns[name], f"{trait}::{name}: the reference takes {count} parameters, the crate's fn takes {sorted(fns[name])}"
             checked += 1
     assert checked >= 45, checked
+
+
+def test_elementwise_and_norm_exports_reject_null_buffers_on_the_host(pkg):
+    """Return code 2 before any launch (nothing here touches a device): the five elementwise exports that used to hand a
+    null pointer straight to their kernel, and the norm-family exports; a count of zero stays a no-op."""
+    lib = pkg.load_library()
+    f, z = C.c_float(1e-6), C.c_size_t
+    one = C.c_void_p(16)                                         # never dereferenced: every call below fails its null check first
+    calls = {
+        "fused_silu_mul_split": lambda: lib.ferrum_hip_fused_silu_mul_split_f16(None, one, 1, 8, None),
+        "fused_silu_mul_split out": lambda: lib.ferrum_hip_fused_silu_mul_split_f16(one, None, 1, 8, None),
+        "fused_gelu_tanh_mul_split": lambda: lib.ferrum_hip_fused_gelu_tanh_mul_split_f16(None, one, 1, 8, None),
+        "fused_gelu_tanh_mul_split out": lambda: lib.ferrum_hip_fused_gelu_tanh_mul_split_f16(one, None, 1, 8, None),
+        "scale_inplace": lambda: lib.ferrum_hip_scale_inplace_f16(None, C.c_float(2.0), z(8), None),
+        "add_inplace": lambda: lib.ferrum_hip_add_inplace_f16(None, one, z(8), None),
+        "add_inplace x": lambda: lib.ferrum_hip_add_inplace_f16(one, None, z(8), None),
+        "add_bias": lambda: lib.ferrum_hip_add_bias_f16(None, one, 1, 8, None),
+        "add_bias bias": lambda: lib.ferrum_hip_add_bias_f16(one, None, 1, 8, None),
+        "fused_add_rms_norm_perm": lambda: lib.ferrum_hip_fused_add_rms_norm_perm_f16(None, one, one, f, one, 1, 8, None, None),
+        "embed_rms_norm": lambda: lib.ferrum_hip_embed_rms_norm_f16(one, None, C.c_float(0.0), None, None, one, f, one, 1, 8, None, 0, None, None),
+        "embed_rms_norm n_zero": lambda: lib.ferrum_hip_embed_rms_norm_f16(one, one, C.c_float(0.0), None, None, one, f, one, 1, 8, None, 4, None, None),
+        "gather_rms_norm": lambda: lib.ferrum_hip_gather_rms_norm_f16(one, None, one, f, one, 1, 8, None),
+        "sandwich_perm": lambda: lib.ferrum_hip_sandwich_add_rms_norm_f32_perm(one, one, None, None, f, None, 1, 8, None, None),
+        "sandwich_slabs": lambda: lib.ferrum_hip_sandwich_add_rms_norm_f32_slabs(None, 1, z(8), 8, one, one, None, f, None, 1, 8, None, None),
+        "sandwich_slabs norm_out": lambda: lib.ferrum_hip_sandwich_add_rms_norm_f32_slabs(one, 1, z(8), 8, one, one, one, f, None, 1, 8, None, None),
+        "fused_gated_act_slabs": lambda: lib.ferrum_hip_fused_gated_act_slabs_f16(None, 1, z(16), 16, one, 1, 8, 0, None),
+        "gather_columns": lambda: lib.ferrum_hip_gather_columns_f16(one, None, one, 1, 8, None),
+    }
+    for name, call in calls.items():
+        assert call() == 2, name
+        assert b"null" in lib.ferrum_hip_last_error() or b"n_zero" in lib.ferrum_hip_last_error(), name
+    assert lib.ferrum_hip_fused_silu_mul_split_f16(None, None, 0, 8, None) == 0
+    assert lib.ferrum_hip_fused_gelu_tanh_mul_split_f16(None, None, 0, 8, None) == 0
+    assert lib.ferrum_hip_scale_inplace_f16(None, C.c_float(2.0), z(0), None) == 0
+    assert lib.ferrum_hip_add_inplace_f16(None, None, z(0), None) == 0
+    assert lib.ferrum_hip_add_bias_f16(None, None, 0, 8, None) == 0

@@ -1,6 +1,7 @@
 """CPU self-test of tests/parity_bounds.py: a clean fp16 GEMM emulation (fp16 inputs, float32 matmul, fp16 store) passes the
 element-wise bound, four single faults a kernel can make are flagged — and on the many-row shape two of them stay below the
-whole-tensor NMSE bucket (1e-6) the suite used alone, which is why the element-wise bound exists."""
+whole-tensor NMSE bucket (1e-6) the suite used alone, which is why the element-wise bound exists.  The second half does the
+same for the norm family's bounds (row norm, sandwich update, slab inputs, gated activations, layer_norm)."""
 import numpy as np
 import pytest
 
@@ -124,3 +125,193 @@ def test_per_vector_kv_checks_see_a_shifted_row_that_the_sequence_nmse_hides():
         pb.assert_kv_positions(ref, got2, pos, pb.KV_ROUNDTRIP_NMSE, pb.kv_vector_nmse, "shifted")
     with pytest.raises(AssertionError, match="position 399, head 2"):
         pb.assert_kv_positions(ref, got2, pos, 0.05, pb.kv_vector_maxerr, "shifted")
+
+
+# ── norm family ──────────────────────────────────────────────────────────────────────────────────────────────────────────
+def _row_ss32(x):
+    """Per-vector fp32 sums of squares [rows, nvec] and their total taken from the last vector to the first (float64
+    sums pairwise from the front: a different order)."""
+    x32 = np.asarray(x, np.float32)
+    ssv = (x32 * x32).reshape(x32.shape[0], -1, 8).sum(axis=-1, dtype=np.float32)
+    total = np.zeros(x32.shape[0], np.float32)
+    for v in range(ssv.shape[1] - 1, -1, -1):
+        total = total + ssv[:, v]
+    return ssv, total
+
+
+def _emu_rms(x, w, eps, total=None, store16=True):
+    """numpy float32 restatement of the row norm; `total` replaces the row sums (fault injection)."""
+    x32, w32 = np.asarray(x, np.float32), np.asarray(w, np.float32)
+    if total is None:
+        total = _row_ss32(x)[1]
+    inv = (np.float32(1.0) / np.sqrt(total / np.float32(x32.shape[1]) + np.float32(eps))).astype(np.float32)
+    y = x32 * inv[:, None] * w32
+    return y.astype(np.float16).astype(np.float32) if store16 else y
+
+
+def _flagged(fn):
+    with pytest.raises(AssertionError, match="outside the element-wise bound"):
+        fn()
+
+
+def _two_ulps(out, r, c):
+    bad = out.copy()
+    h = bad[r, c].astype(np.float16)
+    bad[r, c] = np.float32(np.nextafter(np.nextafter(h, np.float16(np.inf)), np.float16(np.inf)))
+    return bad
+
+
+@pytest.mark.parametrize("eps", [1e-6, 1e-5])
+@pytest.mark.parametrize("dim", [248, 2056, 4104, 8184, 8192, 16384])
+def test_row_norm_bound_passes_clean_emulation_and_flags_each_fault(dim, eps):
+    """Rows of every kind (tests/parity_bounds.norm_rows) at 65 rows; 8192 carries the widest any-order allowance a
+    sandwich kernel can meet, 8184 is the widest row of the 1024-thread form that still has an inactive lane."""
+    rng = np.random.default_rng(dim)
+    rows, nvec = 65, dim // 8
+    x, kinds = pb.norm_rows(rng, rows, dim)
+    w = pb.mixed_sign_weight(rng, dim)
+    clean = _emu_rms(x, w, eps)
+    assert pb.assert_rms_norm_elementwise(x, w, eps, clean, "clean emulation") <= 1.0
+    assert np.all(clean[kinds.index("zero")] == 0.0)
+    ref, _ = pb.rms_norm_ref64(x, w, eps)
+    assert pb.nmse(ref, clean) < NMSE_FP16_TOL
+    ssv, total = _row_ss32(x)
+    faults = {}
+    r, c = kinds.index("normal"), int(np.argmax(np.abs(clean[0]) > 0.5))
+    faults["one element off by two fp16 ulps"] = _two_ulps(clean, r, c)
+    sub = kinds.index("subnormal")                               # the eps-dominated row: a vector an earlier clear left at 0
+    stale = clean.copy()
+    stale[sub, -8:] = 0.0
+    faults["stale last vector"] = stale
+    nb = clean.copy()
+    nb[9] = clean[8]
+    faults["neighbouring row gathered"] = nb
+    faults["last vector left out of the row sum"] = _emu_rms(x, w, eps, total - ssv[:, -1])
+    if nvec > 256:
+        faults["chunk-seam vector counted twice"] = _emu_rms(x, w, eps, total + ssv[:, 256])
+    if nvec < 1024:
+        faults["inactive lanes add vector 0"] = _emu_rms(x, w, eps, total + np.float32(1024 - nvec) * ssv[:, 0])
+    for name, out in faults.items():
+        _flagged(lambda: pb.assert_rms_norm_elementwise(x, w, eps, out, name))
+    # the whole-tensor average passes the first two on this very data (the second once a row has a few hundred vectors)
+    assert pb.nmse(ref, faults["one element off by two fp16 ulps"]) < NMSE_FP16_TOL
+    if dim >= 2056:
+        assert pb.nmse(ref, faults["stale last vector"]) < NMSE_FP16_TOL
+    # fused-add residual and the scaled embedding copies are held bit-exact: one fp16 rounding of an exact fp32 value
+    r16 = pb.f16r(3 * rng.standard_normal((rows, dim)))
+    assert np.array_equal(pb.f16r(r16.astype(np.float64) + x.astype(np.float64)), pb.f16r(r16 + x))
+
+
+@pytest.mark.parametrize("S", [0, 3, 9])
+@pytest.mark.parametrize("dim", [248, 4104, 8192])
+def test_sandwich_bounds_pass_clean_emulation_and_flag_each_fault(dim, S):
+    """residual += rms_norm(branch)·w_branch in fp32, norm_out = fp16(rms_norm(residual)·w_next); S > 0: the branch
+    arrives as S fp32 slabs and is fp16(Σ slabs) by sequential float32 adds."""
+    rng = np.random.default_rng(dim + S)
+    rows, eps, nvec = 65, 1e-6, dim // 8
+    target, kinds = pb.norm_rows(rng, rows, dim, start=1)
+    if S:
+        slabs = pb.split_into_slabs(rng, target, S)
+        branch = pb.slabs_to_f16(slabs)
+        assert np.all(np.isfinite(branch)) and np.all(branch[kinds.index("zero")] == 0.0)
+        assert np.max(np.abs(branch - target)) <= 2.0 ** -10 * np.max(np.abs(target))
+    else:
+        branch = target
+    wb, wn = pb.mixed_sign_weight(rng, dim), pb.mixed_sign_weight(rng, dim)
+    r0 = (3 * rng.standard_normal((rows, dim))).astype(np.float32)
+
+    def emu(total=None, w_first=wb):
+        res = (r0 + _emu_rms(branch, w_first, eps, total, store16=False)).astype(np.float32)
+        return res, _emu_rms(res, wn, eps)
+
+    res, out = emu()
+    assert pb.assert_sandwich_residual(branch, wb, r0, eps, res, "clean residual") <= 1.0
+    assert pb.assert_rms_norm_elementwise(res, wn, eps, out, "clean norm_out") <= 1.0
+    ssv, total = _row_ss32(branch)
+    faulty = {"w_next where w_branch belongs": emu(w_first=wn)[0],
+              "last vector left out of the row sum": emu(total - ssv[:, -1])[0]}
+    if nvec > 256:
+        faulty["chunk-seam vector counted twice"] = emu(total + ssv[:, 256])[0]
+    if nvec < 1024:
+        faulty["inactive lanes add vector 0"] = emu(total + np.float32(1024 - nvec) * ssv[:, 0])[0]
+    nb = res.copy()
+    nb[5] = res[4]
+    faulty["neighbouring row"] = nb
+    for name, bad in faulty.items():
+        _flagged(lambda: pb.assert_sandwich_residual(branch, wb, r0, eps, bad, name))
+    # norm_out is judged from the residual the device returned: a wrong second row sum or a stale vector shows there
+    ssv2, total2 = _row_ss32(res)
+    big2 = int(np.argmax(ssv2.max(axis=1) / total2))             # the row whose energy is most concentrated
+    _flagged(lambda: pb.assert_rms_norm_elementwise(res, wn, eps, _emu_rms(res, wn, eps, total2 - ssv2[:, int(np.argmax(ssv2[big2]))]), "second sum"))
+    _flagged(lambda: pb.assert_rms_norm_elementwise(res, wn, eps, _two_ulps(out, 0, int(np.argmax(np.abs(out[0]) > 0.5))), "two ulps"))
+    if S:                                                        # a slab left out, or summed twice, is a different fp16 branch
+        assert not np.array_equal(pb.slabs_to_f16(slabs[:-1]), branch)
+
+
+@pytest.mark.parametrize("gelu", [False, True])
+@pytest.mark.parametrize("rows,im", [(3, 8), (3, 2056), (2, 4100)])
+def test_gated_activation_bounds_pass_plain_float32_and_flag_faults(rows, im, gelu):
+    gu = pb.gated_inputs(np.random.default_rng(im), rows, im)
+    g, u = gu[:, :im].astype(np.float32), gu[:, im:].astype(np.float32)
+    for v in pb.GATE_PLANTS:
+        assert (g == v).any()
+    with np.errstate(over="ignore"):
+        if gelu:
+            a = np.float32(0.5) * g * (np.float32(1.0) + np.tanh(np.float32(0.79788456) * (g + np.float32(0.044715) * g * g * g)))
+        else:
+            a = g / (np.float32(1.0) + np.exp(-g))
+        with np.errstate(under="ignore"):
+            clean = (a * u).astype(np.float16).astype(np.float32)
+    assert clean.dtype == np.float32 and a.dtype == np.float32
+    assert pb.assert_gated_act_elementwise(gu, clean, gelu) <= 1.0
+    ref = (pb.gelu_tanh_mul_ref64 if gelu else pb.silu_mul_ref64)(g, u)
+    r, c = np.unravel_index(int(np.argmax(np.abs(clean) > 0.5)), clean.shape)
+    _flagged(lambda: pb.assert_gated_act_elementwise(gu, _two_ulps(clean, r, c), gelu))
+    stale = clean.copy()
+    stale[-1, -8:] = clean[0, -8:]
+    _flagged(lambda: pb.assert_gated_act_elementwise(gu, stale, gelu))
+    nb = clean.copy()
+    nb[1] = clean[0]
+    _flagged(lambda: pb.assert_gated_act_elementwise(gu, nb, gelu))
+    if gelu:
+        # the absolute term: at g = −4 an absolute 2^-24 in the bracket is about three fp16 ulps of the result, yet the
+        # bound stays within a few ulps there (a term that swallowed the result would hide a wrong element)
+        g4, u4 = np.float64(-4.0), np.float64(3.0)
+        r4 = pb.gelu_tanh_mul_ref64(g4, u4)
+        t4 = pb.gelu_tanh_mul_tolerance(r4, g4, u4)
+        assert 0.5 * 4 * 3 * 2.0 ** -24 > 2 * 2.0 ** -11 * abs(r4) and t4 < 0.02 * abs(r4)
+    assert ref.shape == clean.shape
+
+
+def test_layer_norm_and_gelu_bounds_pass_float32_emulation_and_flag_faults():
+    rng = np.random.default_rng(4100)
+    rows, dim = 3, 4100
+    x = pb.f16r(rng.standard_normal((rows, dim)) * 3 + 0.7)
+    gam, beta = pb.mixed_sign_weight(rng, dim), pb.f16r(0.1 * rng.standard_normal(dim))
+    x32 = x.astype(np.float32)
+    mean = (x32[:, ::-1].sum(axis=1, dtype=np.float32) / np.float32(dim))[:, None]
+    d = x32 - mean
+    inv = np.float32(1.0) / np.sqrt((d * d).sum(axis=1, dtype=np.float32)[:, None] / np.float32(dim) + np.float32(1e-5))
+    clean = pb.f16r(d * inv * gam + beta)
+    ref, tol = pb.layer_norm_ref_tol(x, gam, beta, 1e-5)
+    assert pb.assert_within(ref, tol, clean, "clean layer_norm") <= 1.0
+    stale = clean.copy()
+    stale[2, -8:] = clean[1, -8:]
+    _flagged(lambda: pb.assert_within(ref, tol, stale, "stale"))
+    nb = clean.copy()
+    nb[1] = clean[0]
+    _flagged(lambda: pb.assert_within(ref, tol, nb, "row"))
+    shifted = pb.f16r((d + np.float32(0.01)) * inv * gam + beta)             # a mean that is off by 0.3 % of the spread
+    _flagged(lambda: pb.assert_within(ref, tol, shifted, "mean"))
+    with pytest.raises(AssertionError, match="offset exceeds"):
+        pb.layer_norm_ref_tol(x + 100.0, gam, beta, 1e-5)
+    # erf-form gelu through the GELU bound with u = 1
+    xs = pb.f16r(np.concatenate([3 * rng.standard_normal(4096), [-4.0, -6.0, 12.0, -12.0]]))
+    z = xs / np.float32(np.sqrt(2.0))
+    t = np.float32(1.0) / (np.float32(1.0) + np.float32(0.3275911) * np.abs(z))
+    y = np.float32(1.0) - (((((np.float32(1.0614054) * t - np.float32(1.4531521)) * t) + np.float32(1.4214138)) * t - np.float32(0.28449672)) * t + np.float32(0.2548296)) * t * np.exp(-z * z)
+    got = pb.f16r(np.float32(0.5) * xs * (np.float32(1.0) + np.where(z < 0, np.float32(-1.0), np.float32(1.0)) * y))
+    gref = pb.gelu_erf_poly_ref64(xs)
+    gtol = pb.gelu_tanh_mul_tolerance(gref, xs)
+    assert pb.assert_within(gref, gtol, got, "clean gelu") <= 1.0
+    _flagged(lambda: pb.assert_within(gref, gtol, _two_ulps(got[None], 0, int(np.argmax(got > 0.5)))[0], "two ulps"))
