@@ -100,6 +100,23 @@ class GptqLinear:
         _check(ctx.lib.ferrum_hip_gptq_linear_forward_f16(self.handle, _ptr(inp), _ptr(out), m, ctx.ws, ctx.stream),
                "gptq_linear_forward")
 
+    def slabs(self, ctx, inp, slabs, m, form, S=0):
+        """The projection as fp32 split-K slabs (form 0 skinny, 1 LDS-shared activations, 2 64-row tiles) into the float32
+        tensor `slabs` → (S used, rows_pad, n_pad)."""
+        s, rp, npad = C.c_int(S), C.c_int(0), C.c_int(0)
+        _check(ctx.lib.ferrum_hip_gptq_linear_slabs_f16(self.handle, _ptr(inp), _ptr(slabs), C.c_size_t(slabs.numel() * 4), m, form,
+                                                        C.byref(s), C.byref(rp), C.byref(npad), ctx.stream), "gptq_linear_slabs")
+        return s.value, rp.value, npad.value
+
+    def can_fuse_tail(self, m):
+        return bool(load_library().ferrum_hip_gptq_linear_can_fuse_tail(self.handle, m))
+
+    def forward_fused_tail(self, ctx, down, weights, residual_in, residual_out, ln_w, eps, top_k, out, m):
+        """forward() whose input rows are the MoE combine + residual add + RMSNorm, made inside the launch (m ≤ 4)."""
+        _check(ctx.lib.ferrum_hip_gptq_linear_forward_fused_tail_f16(self.handle, _ptr(down), _ptr(weights), _ptr(residual_in),
+                                                                     _ptr(residual_out), _ptr(ln_w), C.c_float(eps), top_k, _ptr(out),
+                                                                     m, ctx.ws, ctx.stream), "gptq_linear_forward_fused_tail")
+
     def __del__(self):
         try:
             if self.handle:

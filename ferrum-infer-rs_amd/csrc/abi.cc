@@ -496,6 +496,38 @@ int ferrum_hip_gptq_linear_forward_f16(const FerrumHipGptq* handle, const void* 
     return w4_gemm_dense(g->dev, x, H(out), m, ws ? ws->ptr : nullptr, ws ? ws->bytes : 0, ST(stream));
 }
 
+// op-level entries of the forms only the runner reaches: the fp32 slab producers and the fused combine + add + norm prologue
+int ferrum_hip_gptq_linear_slabs_f16(const FerrumHipGptq* handle, const void* x, float* slabs, size_t slab_bytes, int m, int form,
+                                     int* S_inout, int* rows_pad_out, int* n_pad_out, void* stream) {
+    FH_REQUIRE(handle && S_inout && rows_pad_out && n_pad_out && (m == 0 || (x && slabs)), "gptq_linear_slabs: null argument");
+    FH_REQUIRE(form >= 0 && form <= 2, "gptq_linear_slabs: unknown form %d (0 skinny, 1 LDS-shared activations, 2 64-row tiles)", form);
+    const W4Device& w = handle->dev;
+    FH_REQUIRE(w.num_experts == 1 && w.qw && !w.f16t, "gptq_linear_slabs: handle is not a single INT4 projection");
+    FH_REQUIRE(!w.perm, "gptq_linear_slabs: act-order weights (the runner's producers write the gathered rows themselves)");
+    if (form == 0) {
+        const int S = std::max(1, std::min(*S_inout, w.G));       // the clamp w4_gemm_dense_slabs applies
+        if (int rc = w4_gemm_dense_slabs(w, CH(x), slabs, slab_bytes, m, S, rows_pad_out, n_pad_out, ST(stream))) return rc;
+        *S_inout = S;
+        return 0;
+    }
+    if (form == 1) return w4_gemm_dense_slabs_lds(w, CH(x), slabs, slab_bytes, m, S_inout, rows_pad_out, n_pad_out, ST(stream));
+    return w4_gemm_dense_slabs_tile(w, CH(x), slabs, slab_bytes, m, S_inout, rows_pad_out, n_pad_out, ST(stream));
+}
+
+int ferrum_hip_gptq_linear_forward_fused_tail_f16(const FerrumHipGptq* handle, const void* down, const float* weights,
+                                                  const void* residual_in, void* residual_out, const void* ln_w, float eps, int top_k,
+                                                  void* out, int m, FerrumHipWorkspace* ws, void* stream) {
+    FH_REQUIRE(handle && (m == 0 || (down && weights && residual_in && residual_out && ln_w && out)), "gptq_linear_forward_fused_tail: null argument");
+    FH_REQUIRE(m == 0 || residual_in != residual_out, "gptq_linear_forward_fused_tail: residual_in == residual_out (every workgroup reads, one writes)");
+    FH_REQUIRE(handle->dev.num_experts == 1, "gptq_linear_forward_fused_tail: handle is an expert stack");
+    const FusedCombineNorm fa{CH(down), weights, CH(residual_in), H(residual_out), CH(ln_w), eps, top_k};
+    return w4_gemm_dense(handle->dev, nullptr, H(out), m, ws ? ws->ptr : nullptr, ws ? ws->bytes : 0, ST(stream), &fa);
+}
+
+int ferrum_hip_gptq_linear_can_fuse_tail(const FerrumHipGptq* handle, int m) {
+    return handle && handle->dev.num_experts == 1 && w4_gemm_dense_can_fuse_combine_norm(handle->dev, m) ? 1 : 0;
+}
+
 int ferrum_hip_moe_gemm_phase_f16(const FerrumHipGptq* stack, const void* input, const int32_t* sorted_token_ids,
                                   const int32_t* expert_ids, const int32_t* num_tokens_past_padded, void* output,
                                   int prob_m, int moe_block_size, int top_k, int max_blocks, int fused_silu_mul,

@@ -346,12 +346,19 @@ static int launch_ldsa(const W4Args& a_in, bool has_zp, dim3 grid, hipStream_t s
     return 0;
 }
 
+// LDS of a wgsplit launch: the cross-wave reduction [W][MT·NT·4][64] fp32 — and, with the fused prologue, the m rows (pitch
+// K + 8 halves) and the [W] partial sums of squares (64 floats reserved)
+static size_t wgsplit_lds_bytes(int W, int mt, int nt, bool fused, int m, int k) {
+    size_t lds = (size_t)W * mt * nt * 4 * 64 * sizeof(float);
+    if (fused) lds += (size_t)m * (k + 8) * sizeof(__half) + 64 * sizeof(float);
+    return lds;
+}
+
 template <int MT, int NT>
 static int launch_wgsplit(const W4Args& a, bool has_zp, dim3 grid, int W, hipStream_t stream) {
-    size_t lds = (size_t)W * MT * NT * 4 * 64 * sizeof(float);
+    const size_t lds = wgsplit_lds_bytes(W, MT, NT, MT == 1 && a.fa_down != nullptr, a.M, a.K);
     if constexpr (MT == 1) {
         if (a.fa_down) {                                       // fused combine + add + norm prologue (≤ 4 rows)
-            lds += (size_t)a.M * (a.K + 8) * sizeof(__half) + 64 * sizeof(float);
             FH_REQUIRE(lds <= 64 * 1024, "w4_gemm_dense: fused prologue needs %zu bytes of LDS", lds);
             form_hit(FORM_W4_FUSED_TAIL);
         }
@@ -389,9 +396,38 @@ static int launch_splitk(W4Args& a, const W4Device& w, int S, int rows_pad, floa
     return 0;
 }
 
+// Shape of the intra-workgroup split launch for m rows: NT column tiles per workgroup and W waves (= K slices).  One rule
+// for the dispatcher and for the fused-prologue predicate, which has to know the LDS the launch will ask for.
+struct WgsplitShape { int nt, W; };
+static WgsplitShape wgsplit_shape(const W4Device& w, int m) {
+    const int mt = skinny_row_tiles(m);
+    const int row_blocks = cdiv(m, 16 * mt);
+    const int n16 = w.n64 * 4;
+    // column tiles per workgroup: as wide as possible (A-fragment reuse) while ≥ ~384 workgroups exist
+    int nt = 4;
+    while (nt > 1 && (long)cdiv(n16, nt) * row_blocks < 384) nt >>= 1;
+    // with ≥ 2 row tiles the activation fragments dominate the load traffic: share each across two
+    // column tiles as long as ≥ 128 workgroups remain (measured: qkv 2048→5120 at T=32 10.4 → 7.2 µs)
+    if (mt >= 2 && nt == 1 && (long)cdiv(n16, 2) * row_blocks >= 128) nt = 2;
+    // waves per workgroup (= K slices): enough waves to cover the chip, ≥ 1 group each, LDS ≤ 128 KiB
+    const long wgs = (long)cdiv(n16, nt) * row_blocks;
+    const int w_cap = mt == 1 ? 16 : (mt == 2 ? (nt == 1 ? 16 : 8) : 4);    // matches the kernel's __launch_bounds__
+    int W = 4;
+    while (wgs * W < 2048 && W * 2 <= std::min(w_cap, w.G) && W * 2 * mt * nt * 4 <= 512) W <<= 1;
+    while (W > w.G && W > 1) W >>= 1;
+    const Knobs& kn = knobs();
+    if (kn.w4_nt) nt = kn.w4_nt;        // tuning overrides (development)
+    if (kn.w4_w) W = kn.w4_w;
+    return {nt, W};
+}
+
 // Dense y[M,N] = x[M,K]·Wᵀ (+bias).  One launch: K is split across the waves of each workgroup.
+// The fused prologue keeps its m rows in LDS beside the reduction buffer of the launch w4_gemm_dense would make, so the answer
+// depends on that launch's NT and W: at K = 8192 three rows fit only with W·NT ≤ 15 and four rows never do.
 bool w4_gemm_dense_can_fuse_combine_norm(const W4Device& w, int m) {
-    return m >= 1 && m <= 4 && w.qw != nullptr && w.f16t == nullptr && w.perm == nullptr && w.k % 8 == 0 && w.k <= 8192;
+    if (!(m >= 1 && m <= 4 && w.qw != nullptr && w.f16t == nullptr && w.perm == nullptr && w.k % 8 == 0 && w.k <= 8192)) return false;
+    const WgsplitShape sh = wgsplit_shape(w, m);
+    return wgsplit_lds_bytes(sh.W, 1, sh.nt, true, m, w.k) <= 64 * 1024;
 }
 
 int w4_gemm_dense(const W4Device& w, const __half* x, __half* out, int m, float* workspace,
@@ -471,20 +507,8 @@ int w4_gemm_dense(const W4Device& w, const __half* x, __half* out, int m, float*
         });
     }
     const int n16 = w.n64 * 4;
-    // column tiles per workgroup: as wide as possible (A-fragment reuse) while ≥ ~384 workgroups exist
-    int nt = 4;
-    while (nt > 1 && (long)cdiv(n16, nt) * row_blocks < 384) nt >>= 1;
-    // with ≥ 2 row tiles the activation fragments dominate the load traffic: share each across two
-    // column tiles as long as ≥ 128 workgroups remain (measured: qkv 2048→5120 at T=32 10.4 → 7.2 µs)
-    if (mt >= 2 && nt == 1 && (long)cdiv(n16, 2) * row_blocks >= 128) nt = 2;
-    // waves per workgroup (= K slices): enough waves to cover the chip, ≥ 1 group each, LDS ≤ 128 KiB
-    const long wgs = (long)cdiv(n16, nt) * row_blocks;
-    const int w_cap = mt == 1 ? 16 : (mt == 2 ? (nt == 1 ? 16 : 8) : 4);    // matches the kernel's __launch_bounds__
-    int W = 4;
-    while (wgs * W < 2048 && W * 2 <= std::min(w_cap, w.G) && W * 2 * mt * nt * 4 <= 512) W <<= 1;
-    while (W > w.G && W > 1) W >>= 1;
-    if (kn.w4_nt) nt = kn.w4_nt;        // tuning overrides (development)
-    if (kn.w4_w) W = kn.w4_w;
+    const WgsplitShape sh = wgsplit_shape(w, m);
+    const int nt = sh.nt, W = sh.W;
     dim3 grid(cdiv(n16, nt), row_blocks, 1);
     form_hit(FORM_W4_WGSPLIT);
 #define FH_WG(MTV, NTV) return launch_wgsplit<MTV, NTV>(a, zp, grid, W, stream)

@@ -159,6 +159,28 @@ int ferrum_hip_gptq_info(const FerrumHipGptq* handle, int* k, int* n, int* num_e
 /* out[m,N] = in[m,K]·Wᵀ (+bias) */
 int ferrum_hip_gptq_linear_forward_f16(const FerrumHipGptq* handle, const void* in, void* out, int m,
                                        FerrumHipWorkspace* ws, void* stream);
+/* Op-level entries of the dense forms that otherwise only a model forward reaches (the element-wise parity tests call them).
+ * A null buffer, an unknown `form` and residual_in == residual_out return FERRUM_HIP_INVALID before any launch.
+ *
+ * The projection as fp32 split-K slabs [S][rows_pad][n_pad] (no reduce: the consumer kernel sums them in slab order), through
+ *   form 0  the skinny kernel (any m; S taken from *S_inout, clamped to [1, K/128]; rows_pad = m rounded up to 16 / 32 / 64 for
+ *           m ≤ 16 / ≤ 32 / more),
+ *   form 1  the LDS-shared-activation kernel (17 ≤ m ≤ 32; *S_inout ≤ 0 asks for the launcher's heuristic; rows_pad = 32),
+ *   form 2  the 64-row tile kernel (m ≥ 64; S chosen by the launcher; rows_pad = m rounded up to 64).
+ * n_pad = N rounded up to 64.  *S_inout receives the S used; the consumer reads rows < m and columns < N of each slab, and nothing
+ * beyond the S·rows_pad·n_pad extent is written.  slab_bytes smaller than the extent, bias or act-order weights →
+ * FERRUM_HIP_INVALID. */
+int ferrum_hip_gptq_linear_slabs_f16(const FerrumHipGptq* handle, const void* x, float* slabs, size_t slab_bytes, int m, int form,
+                                     int* S_inout, int* rows_pad_out, int* n_pad_out, void* stream);
+/* out[m,N] = rms_norm(residual_out)·ln_w · Wᵀ with residual_out[t] = fp16(residual_in[t] + Σ_j weights[t·top_k + j]·down[t·top_k + j])
+ * (fp32 sum, j ascending) computed by the GEMM's own workgroups: the MoE tail of the previous layer inside the next q|k|v launch.
+ * down [m·top_k, K] fp16, weights [m·top_k] f32, residual_in / residual_out [m, K] fp16 (distinct buffers), ln_w [K] fp16.
+ * Only where ferrum_hip_gptq_linear_can_fuse_tail(handle, m) answers 1 (m ≤ 4, K ≤ 8192, no act-order, and the m rows fit the
+ * workgroup's LDS beside the reduction buffer of the launch); otherwise FERRUM_HIP_INVALID. */
+int ferrum_hip_gptq_linear_forward_fused_tail_f16(const FerrumHipGptq* handle, const void* down, const float* weights,
+                                                  const void* residual_in, void* residual_out, const void* ln_w, float eps, int top_k,
+                                                  void* out, int m, FerrumHipWorkspace* ws, void* stream);
+int ferrum_hip_gptq_linear_can_fuse_tail(const FerrumHipGptq* handle, int m);
 /* One launch over the align-block routing arrays (moe_block_size 16: one-wave decode kernel; 32 or 64: LDS-tiled prefill
  * kernel; 96 or 128: the tall-tile prefill kernel — K must be a multiple of 256 — whose fp16 weights are (q − zero)·scale
  * rounded once, like the reference's own dequantisation; anything else → FERRUM_HIP_UNSUPPORTED): for every valid sorted id p,

@@ -47,7 +47,12 @@ def sum_tolerance(ref64, absdot64, k, folded):
     return (k * EPS_F32_SUM + (EPS_F16 if folded else 0.0)) * np.asarray(absdot64, np.float64)
 
 
-def gemm_tolerance(ref64, absdot64, k, folded):
+def gemm_tolerance(ref64, absdot64, k, folded, out_f32=False):
+    """out_f32: the result is kept as fp32 (split-K slabs, f32-out GEMMs) — its own rounding is 2^-24·|ref| and there is no
+    fp16 floor (2^-149, the fp32 subnormal, stands in so that an all-zero row has a tolerance).  The float64 sum of S slabs
+    is held by the same bound with the FULL k: slab s carries k_s·2^-23·Σ_s|x||w| of its own part and Σ_s k_s·Σ_s ≤ k·Σ."""
+    if out_f32:
+        return 2.0 ** -24 * np.abs(np.asarray(ref64, np.float64)) + sum_tolerance(ref64, absdot64, k, folded) + 2.0 ** -149
     return EPS_F16 * np.abs(np.asarray(ref64, np.float64)) + sum_tolerance(ref64, absdot64, k, folded) + FLOOR_F16
 
 
@@ -68,10 +73,11 @@ def assert_within(ref64, tol64, got, what=""):
     return float(np.max(err / tol64)) if err.size else 0.0
 
 
-def assert_gemm_elementwise(ref64, absdot64, got, k, folded, what="gemm"):
+def assert_gemm_elementwise(ref64, absdot64, got, k, folded, what="gemm", out_f32=False):
     """|got − ref64| ≤ 2^-11·|ref64| + (k·2^-23 + (2^-11 if folded else 0))·absdot64 + 2^-24 for every element (module
-    docstring).  ref64 = x @ w.T and absdot64 = |x| @ |w|.T in float64; k the length of the sum.  Returns max err/tol."""
-    return assert_within(ref64, gemm_tolerance(ref64, absdot64, k, folded), got, what)
+    docstring; out_f32: gemm_tolerance).  ref64 = x @ w.T and absdot64 = |x| @ |w|.T in float64; k the length of the sum.
+    Returns max err/tol."""
+    return assert_within(ref64, gemm_tolerance(ref64, absdot64, k, folded, out_f32), got, what)
 
 
 def silu64(g):
@@ -105,6 +111,141 @@ def assert_combine_elementwise(down, weights, got, tokens, top_k, what="combine"
     w = np.asarray(weights, np.float64).reshape(tokens, top_k, 1)
     ref, absdot = (d * w).sum(axis=1), (np.abs(d) * np.abs(w)).sum(axis=1)
     return assert_within(ref, gemm_tolerance(ref, absdot, top_k, False), got, what)
+
+
+def fused_tail_residual_ref_tol(down, weights, residual_in, tokens, top_k):
+    """residual_out = fp16(residual_in + Σ_j w_j·down_j) of the fused combine + add + norm prologue → (ref64, tol64):
+
+        tol = [2^-11·|c| + top_k·2^-23·Σ_j|w_j||down_j| + 2^-24] + 2^-11·|r + c|,   c = Σ_j w_j·down_j
+
+    the combine bound (assert_combine_elementwise) plus one fp16 rounding of the add.  The kernel keeps c in fp32 and rounds
+    r + c once to fp32 and once to fp16; the combine bound's own 2^-11·|c| (a rounding this kernel does not make) covers the
+    fp32 add's 2^-24·|r + c| wherever |c| ≥ 2^-13·|r + c|, and the 2^-24 floor below that."""
+    d = np.asarray(down, np.float64).reshape(tokens, top_k, -1)
+    w = np.asarray(weights, np.float64).reshape(tokens, top_k, 1)
+    c, absdot = (d * w).sum(axis=1), (np.abs(d) * np.abs(w)).sum(axis=1)
+    ref = np.asarray(residual_in, np.float64) + c
+    return ref, gemm_tolerance(c, absdot, top_k, False) + EPS_F16 * np.abs(ref)
+
+
+def fused_tail_gemm_ref_tol(residual_out, ln_w, eps, w, bias=None):
+    """out = fp16(x·Wᵀ) of the fused prologue's GEMM, whose input row x is never stored → (ref64, tol64).  The reference is
+    built from the DEVICE's residual_out: x = res·rsqrt(mean(res²) + eps)·ln in float64, ref = x·Wᵀ, and
+
+        tol = 2^-11·|ref| + k·2^-23·Σ|x||w| + 2^-24  +  (2^-11 + k·2^-25 + 8·2^-24)·Σ|x||w|
+
+    The first three terms are the unfolded GEMM bound on the exact x.  The kernel's x̂ differs from x element by element by
+    its fp32 norm arithmetic — a relative k·2^-25 + 8·2^-24 (norm_scale_allowance: the row sum of k squares in any order,
+    /k, +eps, sqrt, divide, two multiplies) — and by the one fp16 rounding of the LDS store, 2^-11: |x̂_i − x_i| ≤
+    (2^-11 + k·2^-25 + 8·2^-24)·|x_i| to first order, so the product moves by at most that times Σ|x||w|."""
+    res = np.asarray(residual_out, np.float64)
+    k = res.shape[-1]
+    x, _ = rms_norm_ref64(res, ln_w, eps)
+    ref, absdot = gemm_refs(x, w, bias)
+    return ref, gemm_tolerance(ref, absdot, k, False) + (EPS_F16 + norm_scale_allowance(k)) * absdot
+
+
+# ── the unfolded INT4 chain (csrc/w4_device.h, w4_consume_group) and the fp16 GEMMs, restated in float32 ─────────────────
+# The bound's accumulation term k·2^-23·Σ|x||w| is derived from "every partial sum ≤ Σ|x||w|".  That does not hold for the
+# unfolded INT4 kernels: a group's chain starts at −1032·S_lo − 72·S_hi (−1024 / −64 with zero points) and adds (1024 + q)·x
+# and (64 + q)·x, so its partial sums are of order 1039·Σ|x| — two orders above Σ|(q − z)·x| — and only the group's END value
+# is small.  The restatements below measure what that costs: `w4_chain_emulate(..., sequential=False)` rounds where the
+# kernel's instruction sequence rounds IF one v_mfma_f32_16x16x32_f16 adds its 32 exact products to the accumulator with a
+# single fp32 rounding (an assumption about the hardware nobody here has measured); sequential=True rounds after every
+# single term, the stated worst-case model.  tests/test_parity_bounds.py runs both at every K the GPU cases use.
+GROUP = 128
+
+
+def unpack_gptq(qweight, qzeros, k, n, group=GROUP):
+    """AutoGPTQ packing → (q [n, k] in 0..15, zero [k/group, n] in 1..16): W[n, k] = (q − zero[k // group, n])·scale."""
+    qw = np.asarray(qweight, np.int64) & 0xFFFFFFFF
+    q = np.stack([(qw >> (4 * j)) & 15 for j in range(8)], axis=1).reshape(k, n)                 # row 8·i + j
+    qz = np.asarray(qzeros, np.int64) & 0xFFFFFFFF
+    z = np.stack([(qz >> (4 * j)) & 15 for j in range(8)], axis=2).reshape(k // group, n)        # column 8·i + j
+    return np.ascontiguousarray(q.T), z + 1
+
+
+def _fl32(a):
+    return np.asarray(a, np.float64).astype(np.float32).astype(np.float64)
+
+
+def w4_chain_parts(x, q, sc, zero, slices, has_zp, sequential=False):
+    """fp32 accumulators of each K slice: x [m, k] fp16-valued, q [n, k], sc / zero [G, n], slices = [(g0, g1), …] in
+    groups → [len(slices), m, n] float32.  Per group (w4_consume_group): t = the offset chain over the four 32-term k-steps
+    (B = −1032 | −72 | −1032 | −72 without zero points, −1024 | −64 | … with), then (1024 + q)·x on k-steps 0 and 2 and
+    (64 + q)·x on 1 and 3, each k-step's exact sum added with ONE fp32 rounding (sequential: one per term); with zero points
+    Σx is a chain of its own and v = fma(−zero, Σx, t); acc = fma(scale, v, acc).  float64 holds every exact intermediate
+    (24-bit × 24-bit products, 32-term sums of 22-bit products)."""
+    x, q = np.asarray(x, np.float64), np.asarray(q, np.float64)
+    sc, zero = np.asarray(sc, np.float64), np.asarray(zero, np.float64)
+    m, n = x.shape[0], q.shape[0]
+    lo_off, hi_off = (-1024.0, -64.0) if has_zp else (-1032.0, -72.0)
+
+    def chain(t, xs, bs):
+        """t ← fl32(t + Σ xs·bs) per k-step (bs [n, 32] or a scalar), or per term."""
+        if np.isscalar(bs):
+            if not sequential:
+                return _fl32(t + (xs.sum(axis=1) * bs)[:, None])
+            for i in range(xs.shape[1]):
+                t = _fl32(t + (xs[:, i] * bs)[:, None])
+            return t
+        if not sequential:
+            return _fl32(t + xs @ bs.T)
+        for i in range(xs.shape[1]):
+            t = _fl32(t + np.outer(xs[:, i], bs[:, i]))
+        return t
+
+    parts = np.zeros((len(slices), m, n))
+    for p, (g0, g1) in enumerate(slices):
+        acc = np.zeros((m, n))
+        for g in range(g0, g1):
+            steps = [slice(g * GROUP + 32 * s, g * GROUP + 32 * s + 32) for s in range(4)]
+            t = np.zeros((m, 1))
+            for s in range(4):
+                t = chain(t, x[:, steps[s]], lo_off if s % 2 == 0 else hi_off)
+            t = np.broadcast_to(t, (m, n)).copy()
+            if has_zp:
+                u = np.zeros((m, 1))
+                for s in range(4):
+                    u = chain(u, x[:, steps[s]], 1.0)
+            # the kernel runs k-steps 0, 1 of every tile, then 2, 3: per accumulator the order is 0, 1, 2, 3
+            for s in range(4):
+                t = chain(t, x[:, steps[s]], q[:, steps[s]] + (1024.0 if s % 2 == 0 else 64.0))
+            v = _fl32(-zero[g][None, :] * u + t) if has_zp else t
+            acc = _fl32(sc[g][None, :] * v + acc)
+        parts[p] = acc
+    return parts.astype(np.float32)
+
+
+def even_slices(G, W):
+    """The K slices [G·w/W, G·(w + 1)/W) of the W waves of a workgroup (or of the S slabs of a split-K grid)."""
+    return [(G * w // W, G * (w + 1) // W) for w in range(W)]
+
+
+def sum_parts(parts, bias=None, bias_times=1, store16=True):
+    """Σ parts in order from 0 in float32 (+ bias, `bias_times` times: fault injection), then the fp16 store."""
+    acc = np.zeros(np.asarray(parts).shape[1:], np.float32)
+    for p in parts:
+        acc = acc + np.asarray(p, np.float32)
+    for _ in range(bias_times if bias is not None else 0):
+        acc = acc + np.asarray(bias, np.float32)[None, :]
+    return acc.astype(np.float16).astype(np.float32) if store16 else acc
+
+
+def f16_gemm_parts(x, w, S, skip_remainder=False):
+    """The fp16 GEMM kernels' split-K: k-steps of 32 in S slices [ks·z/S, ks·(z + 1)/S), each k-step's exact sum added with one
+    fp32 rounding → [S, m, n] float32.  skip_remainder: the k-steps a slice has beyond a multiple of 4 (the kernels' remainder
+    loop after the 4-unrolled main loop) are left out — the fault."""
+    x, w = np.asarray(x, np.float64), np.asarray(w, np.float64)
+    ks = x.shape[1] // 32
+    parts = np.zeros((S, x.shape[0], w.shape[0]))
+    for z in range(S):
+        s0, s1 = ks * z // S, ks * (z + 1) // S
+        if skip_remainder:
+            s1 = s0 + (s1 - s0) // 4 * 4
+        for s in range(s0, s1):
+            parts[z] = _fl32(parts[z] + x[:, 32 * s:32 * s + 32] @ w[:, 32 * s:32 * s + 32].T)
+    return parts.astype(np.float32)
 
 
 # ── paged KV cache, vector by vector ─────────────────────────────────────────────────────────────────────────────────────

@@ -372,3 +372,36 @@ def test_elementwise_and_norm_exports_reject_null_buffers_on_the_host(pkg):
     assert lib.ferrum_hip_scale_inplace_f16(None, C.c_float(2.0), z(0), None) == 0
     assert lib.ferrum_hip_add_inplace_f16(None, None, z(0), None) == 0
     assert lib.ferrum_hip_add_bias_f16(None, None, 0, 8, None) == 0
+
+
+def test_dense_decode_exports_reject_bad_arguments_on_the_host(pkg):
+    """ferrum_hip_gptq_linear_slabs_f16 / _forward_fused_tail_f16 / _can_fuse_tail: null buffers, an unknown form and
+    residual_in == residual_out come back as 2 before the handle is read or anything is launched."""
+    lib = pkg.load_library()
+    one, two = C.c_void_p(16), C.c_void_p(32)                    # never dereferenced: every call below fails a check first
+    s, rp, npad = C.c_int(1), C.c_int(0), C.c_int(0)
+    geo = (C.byref(s), C.byref(rp), C.byref(npad))
+    z, f = C.c_size_t(1 << 20), C.c_float(1e-6)
+    slabs = lambda h, x, sl, form, g=geo: lib.ferrum_hip_gptq_linear_slabs_f16(h, x, sl, z, 1, form, *g, None)
+    tail = lambda h, d, w, ri, ro, ln, out: lib.ferrum_hip_gptq_linear_forward_fused_tail_f16(h, d, w, ri, ro, ln, f, 2, out, 1, None, None)
+    calls = {
+        "slabs handle": (lambda: slabs(None, one, one, 0), b"null"),
+        "slabs x": (lambda: slabs(one, None, one, 0), b"null"),
+        "slabs buffer": (lambda: slabs(one, one, None, 1), b"null"),
+        "slabs S": (lambda: slabs(one, one, one, 0, (None, C.byref(rp), C.byref(npad))), b"null"),
+        "slabs rows_pad": (lambda: slabs(one, one, one, 2, (C.byref(s), None, C.byref(npad))), b"null"),
+        "slabs form 3": (lambda: slabs(one, one, one, 3), b"unknown form"),
+        "slabs form -1": (lambda: slabs(one, one, one, -1), b"unknown form"),
+        "tail handle": (lambda: tail(None, one, one, one, two, one, one), b"null"),
+        "tail down": (lambda: tail(one, None, one, one, two, one, one), b"null"),
+        "tail weights": (lambda: tail(one, one, None, one, two, one, one), b"null"),
+        "tail residual_in": (lambda: tail(one, one, one, None, two, one, one), b"null"),
+        "tail residual_out": (lambda: tail(one, one, one, one, None, one, one), b"null"),
+        "tail ln_w": (lambda: tail(one, one, one, one, two, None, one), b"null"),
+        "tail out": (lambda: tail(one, one, one, one, two, one, None), b"null"),
+        "tail in-place residual": (lambda: tail(one, one, one, one, one, one, one), b"residual_in == residual_out"),
+    }
+    for name, (call, word) in calls.items():
+        assert call() == 2, name
+        assert word in lib.ferrum_hip_last_error(), (name, lib.ferrum_hip_last_error())
+    assert lib.ferrum_hip_gptq_linear_can_fuse_tail(None, 1) == 0
