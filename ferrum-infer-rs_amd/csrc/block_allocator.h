@@ -5,6 +5,7 @@
 // soft-freed blocks be resurrected.  "Bit-exact KV-block indexing" means this class hands out the
 // same ids in the same order as the reference for the same call sequence.
 #pragma once
+#include <stddef.h>
 #include <stdint.h>
 
 #include <unordered_map>

@@ -8,11 +8,9 @@
 
 #include <string>
 
-namespace fh {
+#include "error.h"
 
-// Thread-local error text returned by ferrum_hip_last_error().
-void set_error(const char* fmt, ...);
-const char* last_error();
+namespace fh {
 
 #define FH_CHECK_HIP(expr)                                                              \
     do {                                                                                \
@@ -21,14 +19,6 @@ const char* last_error();
             fh::set_error("%s failed: %s (%s:%d)", #expr, hipGetErrorString(_e), __FILE__, __LINE__); \
             return 1;                                                                   \
         }                                                                               \
-    } while (0)
-
-#define FH_REQUIRE(cond, ...)                 \
-    do {                                      \
-        if (!(cond)) {                        \
-            fh::set_error(__VA_ARGS__);       \
-            return 2;                         \
-        }                                     \
     } while (0)
 
 #define FH_CHECK_LAUNCH()                                                            \

@@ -32,7 +32,7 @@ struct Knobs {
     int sandwich_wide = 1;            // sandwich add + norms of ≤ 64 rows: 1024 threads per row, loads ahead of the reductions (0 = 256 threads)
     int chain_qkv_half = 1;           // decode chain at ≤ 16 rows: q|k|v in 32-column blocks (0 = 64)
     int chain_o_half = 1;             // … and o_proj
-    int chain_split_keys = 256;       // decode chain attention: target keys per KV range (≤ 16 ranges per (sequence, kv head), see runner.hip); 0 = never split
+    int chain_split_keys = 256;       // decode chain attention: target keys per KV range (≤ 16 ranges per (sequence, kv head), see chain_desc in runner_forward.hip); 0 = never split
     int chain_qkv_wide = -1;          // decode chain q|k|v blocks of 128 columns: -1 = where the 64-column blocks + attention exceed chain_slots
     int chain_slots = 256;            // workgroups of the chain kernel the chip holds at once (one per CU)
     int route_gemm_topk = 1;          // prefill router GEMM + top-k as one launch (E = 128)

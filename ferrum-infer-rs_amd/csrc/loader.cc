@@ -9,7 +9,7 @@
 //   * config.json field extraction and per-architecture defaults  ferrum-models/src/definition.rs:225-375,
 //     models/llama_family.rs:596-680,733-810, moe_config.rs:91-130
 //   * tensor names                                        models/llama_family.rs:900-945, qwen3_moe/load.rs:178-260
-// Pure host code: nothing here touches the GPU except through ferrum_hip_model_set_* (runner.hip).
+// Pure host code: nothing here touches the GPU except through ferrum_hip_model_set_* (runner_model.hip).
 #include <fcntl.h>
 #include <sys/mman.h>
 #include <sys/stat.h>

@@ -3,12 +3,11 @@
 // KV admission contract (see include/ferrum_hip.h for file:line citations).
 #pragma once
 #include <memory>
-#include <unordered_map>
 
 #include "../../include/ferrum_hip.h"
-#include "block_allocator.h"
 #include "kernels.h"
 #include "kv_layout.h"
+#include "seq_table.h"
 
 namespace fh {
 
@@ -33,11 +32,6 @@ struct LayerWeights {
     std::vector<int32_t> exp_gate_up_perm_host, exp_down_perm_host;   // act-order stacks: the row permutation every expert of the stack must share
     __half* k_pool = nullptr;
     __half* v_pool = nullptr;
-};
-
-struct SeqState {
-    std::vector<uint32_t> blocks;
-    int len = 0;
 };
 
 // Layout of the per-forward index block (host pinned mirror → device).
@@ -67,13 +61,11 @@ struct FerrumHipModel {
     std::vector<fh::LayerWeights> layers;
 
     // KV
-    std::unique_ptr<fh::BlockAllocator> alloc;
-    std::unordered_map<uint64_t, fh::SeqState> seqs;
-    uint64_t prefix_hits = 0, prefix_misses = 0, prefix_saved_tokens = 0;   // block-level prefix cache probes
+    std::unique_ptr<fh::SeqTable> seqs;   // block allocator, per-sequence block lists and lengths, prefix-cache counters
     // whole-block KV moves (kv_move.hip) behind fork / truncate_kv / kv_swap_out / kv_swap_in
     void** kv_pools_dev = nullptr;        // [2·L] pool base pointers K0, V0, K1, V1, … (built once at finalize)
     uint32_t* kv_pairs_dev = nullptr;     // (src block, dst block) list of the current move; grows on demand
-    size_t kv_pairs_cap = 0;              // … in pairs
+    size_t kv_pairs_bytes = 0;
     uint8_t* kv_staging = nullptr;        // gather / scatter side of a host swap: grows on demand up to KV_STAGING_CAP_BYTES
     size_t kv_staging_bytes = 0;          //   (these calls are host-synchronous and never run inside a capture)
 
@@ -140,7 +132,7 @@ struct FerrumHipModel {
 
     // decode-steps state
     uint32_t* history = nullptr;   // [max_steps, max_seqs] device
-    int history_cap = 0;
+    size_t history_bytes = 0;
     int32_t* step_counter = nullptr;
     hipGraph_t graph = nullptr;
     hipGraphExec_t graph_exec = nullptr;
@@ -154,5 +146,73 @@ struct FerrumHipModel {
     bool comm_owned = false;
     struct FerrumHipTpLoopback* tp_loopback = nullptr;   // in-process test stand-in for the communicator
     __half* tp_tmp = nullptr;
-    size_t tp_tmp_elems = 0;
+    size_t tp_tmp_bytes = 0;
 };
+
+// ── what the runner's translation units share (runner_model / _kv / _tp / _forward / _steps .hip) ──
+namespace fh {
+
+template <typename T>
+int dev_alloc(T** p, size_t count) {
+    *p = nullptr;
+    if (!count) return 0;
+    FH_CHECK_HIP(hipMalloc((void**)p, count * sizeof(T)));
+    FH_CHECK_HIP(hipMemset(*p, 0, count * sizeof(T)));
+    return 0;
+}
+// Grow-on-demand device buffer: nothing while it holds `want` bytes; else wait for the stream (work in flight may still use the
+// old buffer), free it and allocate `want`.  The pointer is null and the capacity zero while the new allocation is pending.
+inline int grow_device(void** p, size_t* cap_bytes, size_t want, hipStream_t s) {
+    if (*cap_bytes >= want) return 0;
+    FH_CHECK_HIP(hipStreamSynchronize(s));
+    if (*p) (void)hipFree(*p);
+    *p = nullptr;
+    *cap_bytes = 0;
+    FH_CHECK_HIP(hipMalloc(p, want));
+    *cap_bytes = want;
+    return 0;
+}
+void f16_to_f32(const __half* src, float* dst, long n, hipStream_t s);   // runner_kv.hip
+
+// runner_tp.hip
+int tp_all_gather(FerrumHipModel* m, const void* in, void* out, size_t bytes);
+int tp_all_reduce(FerrumHipModel* m, __half* buf, size_t count);
+int tp_all_reduce_add_rms_norm(FerrumHipModel* m, __half* x, __half* residual, const __half* w, float eps, __half* out, int T, int H,
+                               hipStream_t s, const int32_t* out_perm);
+
+struct StepShape {
+    int m_total, num_seqs, max_q_len, max_kv_len, num_sampled;
+    bool pure_decode;        // every item is one token AND the model has no uniform sliding window (full-attention decode)
+    bool all_single_token;   // every item is one token (windowed layers included): the fused decode attention applies
+    int single_prefix;       // leading items that bring exactly one token (the decode rows of a mixed batch) …
+    int rest_min_q;          // … and the fewest tokens any item after them brings (0 when there is none)
+};
+
+// The index block (layout m->il) as typed pointers: over the pinned host copy the callers fill, or over the device copy the kernels read
+struct IndexBlock { uint32_t *tokens, *cu, *pos, *kvl; int32_t *sampled_idx, *bt; };
+inline IndexBlock index_block(const FerrumHipModel* m, uint8_t* b) {
+    return {(uint32_t*)(b + m->il.tokens), (uint32_t*)(b + m->il.cu_seqlens), (uint32_t*)(b + m->il.pos_offsets),
+            (uint32_t*)(b + m->il.kv_lens), (int32_t*)(b + m->il.sampled_idx), (int32_t*)(b + m->il.block_tables)};
+}
+
+struct GreedyDeviceOpts {          // device pointers, already uploaded on m->stream
+    const uint8_t* mask = nullptr; int mask_len = 0;
+    const uint32_t* row_offsets = nullptr; const uint32_t* token_ids = nullptr; const float* penalties = nullptr;
+};
+
+// runner_forward.hip
+int enqueue_forward(FerrumHipModel* m, const StepShape& sh, bool greedy, const GreedyDeviceOpts* gopts = nullptr,
+                    const DecodeAdvance* advance = nullptr, int* advance_fused = nullptr);
+const int32_t* moe_ids(const FerrumHipModel* m);
+int moe_max_blocks(int P, int E);
+bool moe_expert_major(const FerrumHipModel* m, int P);
+unsigned* arrive_half(const FerrumHipModel* m, int parity);
+int chain_route_parts(const FerrumHipModel* m);
+MoeRouteLists route_lists(const FerrumHipModel* m, int T, int Q);
+bool moe_pair_rank_lists_ok(const FerrumHipModel* m, const LayerWeights& L, int T, int Q);
+
+// runner_steps.hip
+void drop_graph(FerrumHipModel* m);
+int check_inlaunch_waits(FerrumHipModel* m);
+
+}  // namespace fh

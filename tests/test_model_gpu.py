@@ -716,7 +716,7 @@ def test_decode_chain_yields_to_split_kv_attention_beyond_its_key_limit(pkg, for
 @pytest.mark.parametrize("window", [0, 150])
 def test_decode_chain_attention_kv_splits(pkg, forms, knobs, window):
     """Long contexts inside the chain: the attention role takes several KV ranges per (sequence, kv head) — ≈ `chain_split_keys`
-    keys each (256 by default within a workgroup budget, runner.hip; 16 and 5 ranges forced here), every range's workgroup leaving its (m, l, o) state write-through and taking
+    keys each (256 by default within a workgroup budget, runner_forward.hip; 16 and 5 ranges forced here), every range's workgroup leaving its (m, l, o) state write-through and taking
     a ticket, the last to arrive merging all of them in range order.  Ragged contexts (one shorter than the number of ranges:
     empty ranges), oracle-followed rows, the unsplit chain and the stand-alone launches on the same tokens, graph ≡ eager."""
     from tests import modelgen
