@@ -35,7 +35,6 @@ void reload_knobs() {
     k.attn_rs_min_wgs = env_int("FERRUM_HIP_ATTN_RS_MIN_WGS", 512);
     k.attn_no_rs = env_flag("FERRUM_HIP_ATTN_NO_RS");
     k.attn_narrow = env_flag("FERRUM_HIP_ATTN_NARROW");
-    k.attn_flash32 = env_flag("FERRUM_HIP_ATTN_FLASH32");
     k.attn_no_resident = env_flag("FERRUM_HIP_ATTN_NO_RESIDENT");
     k.attn_resident_min_wgs = env_int("FERRUM_HIP_ATTN_RESIDENT_MIN_WGS", 128);
     k.moe_kw_pairs = env_int("FERRUM_HIP_MOE_KW_PAIRS", 16);

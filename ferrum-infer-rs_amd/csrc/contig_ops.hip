@@ -4,7 +4,7 @@
 // scaled_add_inplace / transpose_token_to_head.  Signatures: traits.rs:225 (flash_attention), :798 (copy_slice),
 // :850 (split_qkv), :897 (qk_norm_rope), :1266 (kv_cache_append_head_major), :1281,1296 (transposes), :1318
 // (scaled_add_inplace); maths cpu.rs:1645-1783, 1993-2060, 2179-2259.
-// The paged lane (rope_kv.hip / attention.hip) is the fast path; these exist so that a backend built on this library
+// The paged lane (rope_kv.hip / attention*.hip) is the fast path; these exist so that a backend built on this library
 // implements the WHOLE core trait, and they are simple, bandwidth-shaped kernels rather than tuned ones.
 #include "common.h"
 #include "kernels.h"

@@ -152,7 +152,7 @@ int gelu_f16(const __half* x, __half* out, long len, hipStream_t s);
 int gather_columns_f16(const __half* in, const int32_t* perm, __half* out, int rows, int cols, hipStream_t s);
 int gather_rows_f16(const __half* in, const int32_t* row_idx, __half* out, int n_rows, int dim, hipStream_t s);
 
-// ── paged KV (rope_kv.hip, attention.hip) ────────────────────────────────────
+// ── paged KV (rope_kv.hip; attention.hip: entry points, attn_plan.h: launch plan, attention_{decode,prefill}.hip: kernels) ──
 // Native pool layout, per (block, kv_head) 4 KiB tiles for head_dim 128 / block 16:
 //   K : [hd/8 chunks][16 keys][8 dims]                — MFMA A-fragment shaped
 //   V : [hd/32][4 key-quads][16 d][2 d-sub][4 keys]    — MFMA B-fragment shaped

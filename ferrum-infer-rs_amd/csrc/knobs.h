@@ -14,7 +14,7 @@
 namespace fh {
 
 struct Knobs {
-    // paged attention (attention.hip)
+    // paged attention (attn_plan.h decides with them)
     bool attn_no_flash = false;
     bool attn_flash_min_rows_set = false;
     long attn_flash_min_rows = 512;
@@ -24,7 +24,6 @@ struct Knobs {
     bool attn_narrow = false;
     bool attn_no_resident = false;    // never take the resident-K/V short-prompt prefill form
     long attn_resident_min_wgs = 128; // … and only from this many workgroups (tests lower it)
-    bool attn_flash32 = false;        // the flash form with 32-key steps (paged_prefill_attn_kernel) for head_dim 128 too
     // INT4 GEMMs (w4_decode.hip, w4_tiles.hip, w4_skinny.hip)
     int moe_kw_pairs = 16;
     int decode_chain = 1;             // MoE decode at ≤ 32 rows: tail + q|k|v + attention + o_proj + route as ONE launch (0 = five launches)

@@ -1,6 +1,6 @@
 // Native paged-KV tile layout (block_size 16).  One (block, kv_head) tile is 16·head_dim fp16
 // (4 KiB at head_dim 128) and is shaped so that ONE coalesced 1-KiB wave load is an MFMA
-// operand fragment of v_mfma_f32_16x16x32_f16 (see attention.hip):
+// operand fragment of v_mfma_f32_16x16x32_f16 (see attention_decode.hip):
 //   K tile : [hd/8 chunks][16 keys][8 dims]             lane (a,b) of load s ↔ key b, chunk 4s+a
 //   V tile : [hd/32][4 key-quads][16 d][2 d-sub][4 keys]  lane (a,b) of load p ↔ keys 4a..4a+3,
 //                                                        dims 32p+b and 32p+16+b

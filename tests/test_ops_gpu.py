@@ -2,6 +2,8 @@
 same seeded inputs.  Tolerances are the reference's own op_diff buckets
 (ferrum-testkit/src/op_diff/mod.rs:46-49: NMSE fp16 1e-6, attention 5e-3, fp16 round-trip 3e-3)
 unless a tighter one is written in the test; integer outputs are bit-exact."""
+import types
+
 import numpy as np
 import pytest
 
@@ -486,6 +488,31 @@ def _fill_pool(env, K, V, tables, kv_lens, nkv, hd, num_blocks):
     return ck, cv
 
 
+def _paged_batch(env, rng, kv_lens, nq, nkv, hd, q_lens=None, spare_blocks=1, spare_columns=0):
+    """The paged batch the attention tests run on: block tables over a permuted pool (`spare_blocks` more blocks than the sequences
+    hold, `spare_columns` more table columns than the longest needs), per-sequence K / V [len, nkv, hd] written through _fill_pool,
+    and for `q_lens` the cu_seqlens and q [Σ q_lens, nq, hd].  Draws from `rng` in this order: the permutation, K then V of each
+    sequence, q."""
+    S = len(kv_lens)
+    b = types.SimpleNamespace(max_blocks=(max(kv_lens) + 15) // 16 + spare_columns,
+                              num_blocks=sum((n + 15) // 16 for n in kv_lens) + spare_blocks, K=[], V=[])
+    perm = rng.permutation(b.num_blocks)
+    b.tables = np.zeros((S, b.max_blocks), np.int32)
+    used = 0
+    for s, n in enumerate(kv_lens):
+        nb = (n + 15) // 16
+        b.tables[s, :nb] = perm[used:used + nb]
+        used += nb
+        b.K.append(f16r(rng.standard_normal((n, nkv, hd))))
+        b.V.append(f16r(rng.standard_normal((n, nkv, hd))))
+    b.ck, b.cv = _fill_pool(env, b.K, b.V, b.tables, kv_lens, nkv, hd, b.num_blocks)
+    if q_lens is not None:
+        b.m_total = sum(q_lens)
+        b.cu = np.concatenate([[0], np.cumsum(q_lens)]).astype(np.int32)
+        b.q = f16r(rng.standard_normal((b.m_total, nq, hd)))
+    return b
+
+
 def _ref_attention(O, q, K, V, pos_offset, nq, nkv, hd, window=0):
     """q [T,nq,hd] at positions pos_offset.. over K/V [len,nkv,hd] → [T,nq,hd] (cpu.rs:2179-2259)."""
     T, kv_len = q.shape[0], K.shape[0]
@@ -517,20 +544,9 @@ def test_paged_batched_decode_attention(env, nq, nkv, hd, kv_lens):
     pkg, B, ctx, O, torch = env
     rng = np.random.default_rng(nq + nkv + hd + len(kv_lens))
     S = len(kv_lens)
-    max_blocks = (max(kv_lens) + 15) // 16 + 1
-    num_blocks = sum((n + 15) // 16 for n in kv_lens) + 3
-    perm = rng.permutation(num_blocks)
-    tables = np.zeros((S, max_blocks), np.int32)
-    used = 0
-    K, V = [], []
-    for s, n in enumerate(kv_lens):
-        nb = (n + 15) // 16
-        tables[s, :nb] = perm[used:used + nb]
-        used += nb
-        K.append(f16r(rng.standard_normal((n, nkv, hd))))
-        V.append(f16r(rng.standard_normal((n, nkv, hd))))
-    ck, cv = _fill_pool(env, K, V, tables, kv_lens, nkv, hd, num_blocks)
-    q = f16r(rng.standard_normal((S, nq, hd)))
+    b = _paged_batch(env, rng, kv_lens, nq, nkv, hd, q_lens=[1] * S, spare_blocks=3, spare_columns=1)
+    tables, K, V, ck, cv, max_blocks = b.tables, b.K, b.V, b.ck, b.cv, b.max_blocks
+    q = b.q
     out = torch.empty(S, nq, hd, dtype=torch.float16, device="cuda")
     B.paged_batched_decode_attention(ctx, dev16(torch, q), ck, cv, out, torch.from_numpy(tables).cuda(),
                                      torch.from_numpy(np.array(kv_lens, np.int32)).cuda(), S, max(kv_lens), nq, nkv, hd,
@@ -556,21 +572,9 @@ def test_paged_varlen_attention_mixed_batch(env, window, nq, nkv, hd, knobs, for
     q_lens, pos_offs = [37, 1, 16, 3], [0, 90, 20, 250]       # fresh prefill, decode, chunk, late chunk
     S = len(q_lens)
     kv_lens = [p + t for p, t in zip(pos_offs, q_lens)]
-    max_blocks = (max(kv_lens) + 15) // 16
-    num_blocks = sum((n + 15) // 16 for n in kv_lens) + 1
-    perm = rng.permutation(num_blocks)
-    tables = np.zeros((S, max_blocks), np.int32)
-    used, K, V = 0, [], []
-    for s, n in enumerate(kv_lens):
-        nb = (n + 15) // 16
-        tables[s, :nb] = perm[used:used + nb]
-        used += nb
-        K.append(f16r(rng.standard_normal((n, nkv, hd))))
-        V.append(f16r(rng.standard_normal((n, nkv, hd))))
-    ck, cv = _fill_pool(env, K, V, tables, kv_lens, nkv, hd, num_blocks)
-    m_total = sum(q_lens)
-    cu = np.concatenate([[0], np.cumsum(q_lens)]).astype(np.int32)
-    q = f16r(rng.standard_normal((m_total, nq, hd)))
+    b = _paged_batch(env, rng, kv_lens, nq, nkv, hd, q_lens=q_lens)
+    tables, K, V, ck, cv, max_blocks = b.tables, b.K, b.V, b.ck, b.cv, b.max_blocks
+    m_total, cu, q = b.m_total, b.cu, b.q
     out = torch.zeros(m_total, nq, hd, dtype=torch.float16, device="cuda")
     B.paged_varlen_attention(ctx, dev16(torch, q), ck, cv, out, torch.from_numpy(cu).cuda(),
                              torch.from_numpy(np.array(pos_offs, np.int32)).cuda(), torch.from_numpy(tables).cuda(), S,
@@ -583,7 +587,7 @@ def test_paged_varlen_attention_mixed_batch(env, window, nq, nkv, hd, knobs, for
         assert nmse(ref, got[cu[s]:cu[s + 1]]) < 1e-5, s
     if window == 0:
         # the paged reference (attention.rs:30-114) agrees for the fresh-prefill sequence
-        pk = np.zeros((num_blocks, 16, nkv, hd), np.float32)
+        pk = np.zeros((b.num_blocks, 16, nkv, hd), np.float32)
         pv = np.zeros_like(pk)
         for p in range(kv_lens[0]):
             pk[tables[0, p // 16], p % 16] = K[0][p]
@@ -602,21 +606,9 @@ def test_paged_varlen_attention_many_prefill_tiles_row_split(env, window, knobs,
     nq, nkv, hd, S, T = 8, 4, 128, 24, 200
     q_lens, pos_offs = [T] * S, [0] * (S - 2) + [48, 5]            # two of them continue an existing context
     kv_lens = [p + t for p, t in zip(pos_offs, q_lens)]
-    max_blocks = (max(kv_lens) + 15) // 16
-    num_blocks = sum((n + 15) // 16 for n in kv_lens) + 1
-    perm = rng.permutation(num_blocks)
-    tables = np.zeros((S, max_blocks), np.int32)
-    used, K, V = 0, [], []
-    for s, n in enumerate(kv_lens):
-        nb = (n + 15) // 16
-        tables[s, :nb] = perm[used:used + nb]
-        used += nb
-        K.append(f16r(rng.standard_normal((n, nkv, hd))))
-        V.append(f16r(rng.standard_normal((n, nkv, hd))))
-    ck, cv = _fill_pool(env, K, V, tables, kv_lens, nkv, hd, num_blocks)
-    m_total = sum(q_lens)
-    cu = np.concatenate([[0], np.cumsum(q_lens)]).astype(np.int32)
-    q = f16r(rng.standard_normal((m_total, nq, hd)))
+    b = _paged_batch(env, rng, kv_lens, nq, nkv, hd, q_lens=q_lens)
+    tables, K, V, ck, cv, max_blocks = b.tables, b.K, b.V, b.ck, b.cv, b.max_blocks
+    m_total, cu, q = b.m_total, b.cu, b.q
     out = torch.zeros(m_total, nq, hd, dtype=torch.float16, device="cuda")
     B.paged_varlen_attention(ctx, dev16(torch, q), ck, cv, out, torch.from_numpy(cu).cuda(),
                              torch.from_numpy(np.array(pos_offs, np.int32)).cuda(), torch.from_numpy(tables).cuda(), S,
@@ -640,21 +632,9 @@ def test_paged_prefill_attention_lds_shared_kv(env, window, nq, nkv, hd, knobs, 
     q_lens, pos_offs = [70, 33, 64, 17, 49], [0, 90, 20, 5, 300]
     S = len(q_lens)
     kv_lens = [p + t for p, t in zip(pos_offs, q_lens)]
-    max_blocks = (max(kv_lens) + 15) // 16
-    num_blocks = sum((n + 15) // 16 for n in kv_lens) + 1
-    perm = rng.permutation(num_blocks)
-    tables = np.zeros((S, max_blocks), np.int32)
-    used, K, V = 0, [], []
-    for s, n in enumerate(kv_lens):
-        nb = (n + 15) // 16
-        tables[s, :nb] = perm[used:used + nb]
-        used += nb
-        K.append(f16r(rng.standard_normal((n, nkv, hd))))
-        V.append(f16r(rng.standard_normal((n, nkv, hd))))
-    ck, cv = _fill_pool(env, K, V, tables, kv_lens, nkv, hd, num_blocks)
-    m_total = sum(q_lens)
-    cu = np.concatenate([[0], np.cumsum(q_lens)]).astype(np.int32)
-    q = f16r(rng.standard_normal((m_total, nq, hd)))
+    b = _paged_batch(env, rng, kv_lens, nq, nkv, hd, q_lens=q_lens)
+    tables, K, V, ck, cv, max_blocks = b.tables, b.K, b.V, b.ck, b.cv, b.max_blocks
+    m_total, cu, q = b.m_total, b.cu, b.q
     out = torch.full((m_total + 1, nq, hd), 9.0, dtype=torch.float16, device="cuda")      # guard row
     B.paged_varlen_attention(ctx, dev16(torch, q), ck, cv, out, torch.from_numpy(cu).cuda(),
                              torch.from_numpy(np.array(pos_offs, np.int32)).cuda(), torch.from_numpy(tables).cuda(), S,
@@ -681,21 +661,9 @@ def test_paged_prefill_attention_resident_kv(env, window, nq, nkv, knobs, forms)
     S = len(q_lens)
     kv_lens = [p + t for p, t in zip(pos_offs, q_lens)]
     assert max(kv_lens) <= 256
-    max_blocks = (max(kv_lens) + 15) // 16
-    num_blocks = sum((n + 15) // 16 for n in kv_lens) + 1
-    perm = rng.permutation(num_blocks)
-    tables = np.zeros((S, max_blocks), np.int32)
-    used, K, V = 0, [], []
-    for s_, n in enumerate(kv_lens):
-        nb = (n + 15) // 16
-        tables[s_, :nb] = perm[used:used + nb]
-        used += nb
-        K.append(f16r(rng.standard_normal((n, nkv, hd))))
-        V.append(f16r(rng.standard_normal((n, nkv, hd))))
-    ck, cv = _fill_pool(env, K, V, tables, kv_lens, nkv, hd, num_blocks)
-    m_total = sum(q_lens)
-    cu = np.concatenate([[0], np.cumsum(q_lens)]).astype(np.int32)
-    q = f16r(rng.standard_normal((m_total, nq, hd)))
+    b = _paged_batch(env, rng, kv_lens, nq, nkv, hd, q_lens=q_lens)
+    tables, K, V, ck, cv, max_blocks = b.tables, b.K, b.V, b.ck, b.cv, b.max_blocks
+    m_total, cu, q = b.m_total, b.cu, b.q
     out = torch.full((m_total + 1, nq, hd), 9.0, dtype=torch.float16, device="cuda")      # guard row
     B.paged_varlen_attention(ctx, dev16(torch, q), ck, cv, out, torch.from_numpy(cu).cuda(),
                              torch.from_numpy(np.array(pos_offs, np.int32)).cuda(), torch.from_numpy(tables).cuda(), S,
@@ -719,21 +687,9 @@ def test_paged_prefill_attention_lds_shared_kv_many_sequences(env, knobs, forms)
     q_lens[0], q_lens[64] = 0, 0
     pos_offs = [int(x) for x in rng.integers(0, 40, size=S)]
     kv_lens = [p + t for p, t in zip(pos_offs, q_lens)]
-    max_blocks = (max(kv_lens) + 15) // 16
-    num_blocks = sum((n + 15) // 16 for n in kv_lens) + 1
-    perm = rng.permutation(num_blocks)
-    tables = np.zeros((S, max_blocks), np.int32)
-    used, K, V = 0, [], []
-    for s, n in enumerate(kv_lens):
-        nb = (n + 15) // 16
-        tables[s, :nb] = perm[used:used + nb]
-        used += nb
-        K.append(f16r(rng.standard_normal((n, nkv, hd))))
-        V.append(f16r(rng.standard_normal((n, nkv, hd))))
-    ck, cv = _fill_pool(env, K, V, tables, kv_lens, nkv, hd, num_blocks)
-    m_total = sum(q_lens)
-    cu = np.concatenate([[0], np.cumsum(q_lens)]).astype(np.int32)
-    q = f16r(rng.standard_normal((m_total, nq, hd)))
+    b = _paged_batch(env, rng, kv_lens, nq, nkv, hd, q_lens=q_lens)
+    tables, K, V, ck, cv, max_blocks = b.tables, b.K, b.V, b.ck, b.cv, b.max_blocks
+    m_total, cu, q = b.m_total, b.cu, b.q
     out = torch.zeros(m_total, nq, hd, dtype=torch.float16, device="cuda")
     B.paged_varlen_attention(ctx, dev16(torch, q), ck, cv, out, torch.from_numpy(cu).cuda(),
                              torch.from_numpy(np.array(pos_offs, np.int32)).cuda(), torch.from_numpy(tables).cuda(), S,
@@ -748,25 +704,50 @@ def test_paged_prefill_attention_lds_shared_kv_many_sequences(env, knobs, forms)
         assert nmse(ref, got[cu[s]:cu[s + 1]]) < 1e-5, s
 
 
+@pytest.mark.parametrize("no_rs", [False, True])
+def test_paged_varlen_attention_compact_grid_many_sequences(env, no_rs, knobs, forms):
+    """The compact grid of the row-split and the KV-split form over 70 sequences (two passes of the in-kernel sequence lookup):
+    69 decode-like sequences of 1 … 3 tokens, one of them empty, and at index 66 — found in the second pass — a 200-token prompt.
+    328 tokens × GQA group 2: 25 row tiles for the longest sequence and 70·7·2 = 980 work-groups, so row-split on its own heuristic,
+    ⌈111 / 4⌉ + 70 = 98 units against a grid of 490; KV-split (ATTN_NO_RS) with 111 units against 1750 tiles."""
+    pkg, B, ctx, O, torch = env
+    if no_rs:
+        knobs.set(ATTN_NO_RS=1)
+    rng = np.random.default_rng(7066)
+    nq, nkv, hd, S = 4, 2, 128, 70
+    q_lens = [int(x) for x in rng.integers(1, 4, size=S)]
+    q_lens[9], q_lens[66] = 0, 200
+    pos_offs = [int(x) for x in rng.integers(0, 41, size=S)]
+    pos_offs[9] = 5
+    kv_lens = [p + t for p, t in zip(pos_offs, q_lens)]
+    b = _paged_batch(env, rng, kv_lens, nq, nkv, hd, q_lens=q_lens)
+    out = torch.full((b.m_total + 1, nq, hd), 9.0, dtype=torch.float16, device="cuda")      # guard row
+    B.paged_varlen_attention(ctx, dev16(torch, b.q), b.ck, b.cv, out, torch.from_numpy(b.cu).cuda(),
+                             torch.from_numpy(np.array(pos_offs, np.int32)).cuda(), torch.from_numpy(b.tables).cuda(), S,
+                             b.m_total, max(kv_lens), nq, nkv, hd, 0, 16, b.max_blocks, max(q_lens))
+    ctx.sync()
+    if no_rs:
+        forms.require("attn_kv_narrow", absent=("attn_row_split", "attn_flash", "attn_resident", "attn_split_reduce"))
+    else:
+        forms.require("attn_row_split", absent=("attn_kv_narrow", "attn_flash", "attn_resident", "attn_split_reduce"))
+    got = host(out)
+    assert np.all(got[b.m_total] == 9.0)
+    for s in range(S):
+        if q_lens[s] == 0:
+            continue
+        ref = _ref_attention(O, b.q[b.cu[s]:b.cu[s + 1]], b.K[s], b.V[s], pos_offs[s], nq, nkv, hd, 0)
+        assert nmse(ref, got[b.cu[s]:b.cu[s + 1]]) < 1e-5, s
+
+
 def test_paged_decode_long_context_split_kv(env, forms):
     # exercises the grid.z flash-decode split + reduce at a BASELINE-like head config (Qwen3-30B: 32/4 heads)
     pkg, B, ctx, O, torch = env
     rng = np.random.default_rng(3)
     nq, nkv, hd, kv_lens = 32, 4, 128, [4096, 1500]
     S = 2
-    max_blocks = (max(kv_lens) + 15) // 16
-    num_blocks = sum((n + 15) // 16 for n in kv_lens)
-    tables = np.zeros((S, max_blocks), np.int32)
-    perm = rng.permutation(num_blocks)
-    used, K, V = 0, [], []
-    for s, n in enumerate(kv_lens):
-        nb = (n + 15) // 16
-        tables[s, :nb] = perm[used:used + nb]
-        used += nb
-        K.append(f16r(rng.standard_normal((n, nkv, hd))))
-        V.append(f16r(rng.standard_normal((n, nkv, hd))))
-    ck, cv = _fill_pool(env, K, V, tables, kv_lens, nkv, hd, num_blocks)
-    q = f16r(rng.standard_normal((S, nq, hd)))
+    b = _paged_batch(env, rng, kv_lens, nq, nkv, hd, q_lens=[1] * S, spare_blocks=0)
+    tables, K, V, ck, cv, max_blocks = b.tables, b.K, b.V, b.ck, b.cv, b.max_blocks
+    q = b.q
     q[0, 3] *= 6.0                                          # a peaked row: forces large online-softmax rescales
     out = torch.empty(S, nq, hd, dtype=torch.float16, device="cuda")
     B.paged_batched_decode_attention(ctx, dev16(torch, q), ck, cv, out, torch.from_numpy(tables).cuda(),
@@ -790,18 +771,8 @@ def test_paged_decode_attention_fused_qkv_equals_two_op_chain(env, nq, nkv, hd, 
     pkg, B, ctx, O, torch = env
     rng = np.random.default_rng(nq * 3 + nkv + hd + len(kv_lens) + qk_mode)
     S = len(kv_lens)
-    max_blocks = (max(kv_lens) + 15) // 16 + 1
-    num_blocks = sum((n + 15) // 16 for n in kv_lens) + 3
-    perm = rng.permutation(num_blocks)
-    tables = np.zeros((S, max_blocks), np.int32)
-    used, K, V = 0, [], []
-    for s, n in enumerate(kv_lens):
-        nb = (n + 15) // 16
-        tables[s, :nb] = perm[used:used + nb]
-        used += nb
-        K.append(f16r(rng.standard_normal((n, nkv, hd))))      # the last slot holds stale values the step overwrites
-        V.append(f16r(rng.standard_normal((n, nkv, hd))))
-    ck, cv = _fill_pool(env, K, V, tables, kv_lens, nkv, hd, num_blocks)
+    b = _paged_batch(env, rng, kv_lens, nq, nkv, hd, spare_blocks=3, spare_columns=1)    # (the last slot of each sequence holds stale values the step overwrites)
+    tables, ck, cv, max_blocks = b.tables, b.ck, b.cv, b.max_blocks
     ck2, cv2 = ck.clone(), cv.clone()
     cos, sin = _rope(O, hd, max(kv_lens) + 1)
     cosd, sind = torch.from_numpy(cos).cuda(), torch.from_numpy(sin).cuda()
@@ -1428,21 +1399,11 @@ def test_paged_decode_attention_trait_form(env, nq, nkv, hd, q_len, ctx_len):
     rng = np.random.default_rng(nq + q_len + ctx_len)
     S = 3 if q_len == 1 else 1
     kv_lens = [ctx_len, 17, 130][:S]
-    max_blocks = (max(kv_lens) + 15) // 16 + 1
-    num_blocks = sum((n + 15) // 16 for n in kv_lens) + 2
-    perm = rng.permutation(num_blocks)
-    tables = np.zeros((S, max_blocks), np.int32)
-    used, K, V = 0, [], []
-    for s, n in enumerate(kv_lens):
-        nb = (n + 15) // 16
-        tables[s, :nb] = perm[used:used + nb]
-        used += nb
-        K.append(f16r(rng.standard_normal((n, nkv, hd))))
-        V.append(f16r(rng.standard_normal((n, nkv, hd))))
-    ck, cv = _fill_pool(env, K, V, tables, kv_lens, nkv, hd, num_blocks)
+    b = _paged_batch(env, rng, kv_lens, nq, nkv, hd, q_lens=[1] * S if q_len == 1 else [q_len], spare_blocks=2, spare_columns=1)
+    tables, K, V, ck, cv, max_blocks = b.tables, b.K, b.V, b.ck, b.cv, b.max_blocks
     lens_d = torch.from_numpy(np.array(kv_lens, np.int32)).cuda()
     if q_len == 1:
-        q = f16r(rng.standard_normal((S, nq, hd)))
+        q = b.q
         out = torch.zeros(S, nq, hd, dtype=torch.float16, device="cuda")
         B.paged_decode_attention(ctx, dev16(torch, q), ck, cv, out, torch.from_numpy(tables).cuda(), lens_d, S, nq, nkv, hd, 16, max_blocks, 1)
         ctx.sync()
@@ -1450,7 +1411,7 @@ def test_paged_decode_attention_trait_form(env, nq, nkv, hd, q_len, ctx_len):
         for s, n in enumerate(kv_lens):
             assert nmse(_ref_attention(O, q[s:s + 1], K[s], V[s], n - 1, nq, nkv, hd), got[s:s + 1]) < 1e-5, s
     else:
-        q_tm = f16r(rng.standard_normal((q_len, nq, hd)))        # token-major for the reference …
+        q_tm = b.q                                               # token-major for the reference …
         q_hm = np.ascontiguousarray(q_tm.transpose(1, 0, 2))     # … head-major for the call
         out = torch.zeros(nq, q_len, hd, dtype=torch.float16, device="cuda")
         B.paged_decode_attention(ctx, dev16(torch, q_hm), ck, cv, out, torch.from_numpy(tables).cuda(), lens_d, 1, nq, nkv, hd, 16, max_blocks, q_len)
