@@ -1,16 +1,14 @@
-// C-ABI layer (include/ferrum_hip.h) over the gfx950 kernels: argument validation, handles,
-// memory, and the native-operator descriptor.  Host-only code; compiled with hipcc.
+// C-ABI layer (include/ferrum_hip.h) over the gfx950 kernels: the error text, device / stream / memory / event / workspace /
+// graph calls, the thin op wrappers (argument validation, then the fh:: launcher), the block allocator and the
+// native-operator descriptor.  Host-only code; compiled with hipcc.  The GPTQ / expert-stack handle is abi_gptq.cc.
 #include <stdarg.h>
 
-#include <mutex>
-
 #include "../../include/ferrum_hip.h"
+#include "abi_private.h"
 #include "block_allocator.h"
 #include "common.h"
 #include "kernels.h"
 #include "knobs.h"
-
-#include <atomic>
 
 namespace fh {
 static thread_local char g_err[1024] = "";
@@ -21,101 +19,14 @@ void set_error(const char* fmt, ...) {
     va_end(ap);
 }
 const char* last_error() { return g_err; }
-
-// ── development knobs (read once) and kernel-form accounting ────────────────
-static Knobs g_knobs;
-static int env_int(const char* name, int dflt) { const char* e = getenv(name); return e ? atoi(e) : dflt; }
-static bool env_flag(const char* name) { const char* e = getenv(name); return e && atoi(e) != 0; }
-void reload_knobs() {
-    Knobs k;
-    k.attn_no_flash = env_flag("FERRUM_HIP_ATTN_NO_FLASH");
-    k.attn_flash_min_rows_set = getenv("FERRUM_HIP_ATTN_FLASH_MIN_ROWS") != nullptr;
-    k.attn_flash_min_rows = env_int("FERRUM_HIP_ATTN_FLASH_MIN_ROWS", 512);
-    k.attn_splits = env_int("FERRUM_HIP_ATTN_SPLITS", 0);
-    k.attn_rs_min_wgs = env_int("FERRUM_HIP_ATTN_RS_MIN_WGS", 512);
-    k.attn_no_rs = env_flag("FERRUM_HIP_ATTN_NO_RS");
-    k.attn_narrow = env_flag("FERRUM_HIP_ATTN_NARROW");
-    k.attn_no_resident = env_flag("FERRUM_HIP_ATTN_NO_RESIDENT");
-    k.attn_resident_min_wgs = env_int("FERRUM_HIP_ATTN_RESIDENT_MIN_WGS", 128);
-    k.moe_kw_pairs = env_int("FERRUM_HIP_MOE_KW_PAIRS", 16);
-    k.moe_em2 = env_int("FERRUM_HIP_MOE_EM2", 1);
-    k.decode_chain = env_int("FERRUM_HIP_DECODE_CHAIN", 1);
-    k.moe_deferred_merge = env_int("FERRUM_HIP_MOE_DEFERRED_MERGE", 1);
-    k.moe_pair_rank_lists = env_int("FERRUM_HIP_MOE_PAIR_RANK_LISTS", 1);
-    k.dense_chain = env_int("FERRUM_HIP_DENSE_CHAIN", 1);
-    k.chain_max_keys = env_int("FERRUM_HIP_CHAIN_MAX_KEYS", 4096);
-    k.chain_split_keys = env_int("FERRUM_HIP_CHAIN_SPLIT_KEYS", 256);
-    k.chain_attn_splits = env_int("FERRUM_HIP_CHAIN_ATTN_SPLITS", 0);
-    k.route_gemm_topk = env_int("FERRUM_HIP_ROUTE_GEMM_TOPK", 1);
-    k.chain_qkv_wide = env_int("FERRUM_HIP_CHAIN_QKV_WIDE", -1);
-    k.chain_slots = env_int("FERRUM_HIP_CHAIN_SLOTS", 256);
-    k.chain_o_half = env_int("FERRUM_HIP_CHAIN_O_HALF", 1);
-    k.chain_qkv_half = env_int("FERRUM_HIP_CHAIN_QKV_HALF", 1);
-    k.sandwich_wide = env_int("FERRUM_HIP_SANDWICH_WIDE", 1);
-    k.chain_max_rows = std::min(128, env_int("FERRUM_HIP_CHAIN_MAX_ROWS", 128));
-    k.w4_tile_min_m = env_int("FERRUM_HIP_W4_TILE_MIN_M", 0);
-    k.w4_tile_wgs = env_int("FERRUM_HIP_W4_TILE_WGS", 256);
-    k.w4_ldsa = env_int("FERRUM_HIP_W4_LDSA", 1);
-    k.w4_ldsa_nw = env_int("FERRUM_HIP_W4_LDSA_NW", 0);
-    k.w4_ldsa_s = env_int("FERRUM_HIP_W4_LDSA_S", 0);
-    k.w4_big = env_int("FERRUM_HIP_W4_BIG", 0);
-    k.w4_nt = env_int("FERRUM_HIP_W4_NT", 0);
-    k.w4_w = env_int("FERRUM_HIP_W4_W", 0);
-    k.lds_min_wgs = env_int("FERRUM_HIP_LDS_MIN_WGS", 128);
-    k.lds_min_groups = env_int("FERRUM_HIP_LDS_MIN_GROUPS", 8);
-    k.no_graph = getenv("FERRUM_HIP_NO_GRAPH") != nullptr;
-    k.trace_launches = getenv("FERRUM_HIP_TRACE_LAUNCHES") != nullptr && k.no_graph;
-    k.time_same_layer = getenv("FERRUM_HIP_TIME_SAME_LAYER") != nullptr;
-    k.tp_oneshot = env_int("FERRUM_HIP_TP_ONESHOT", -1);
-    k.tp_fused_norm = env_int("FERRUM_HIP_TP_FUSED_NORM", 1);
-    g_knobs = k;
-}
-namespace { struct KnobsInit { KnobsInit() { reload_knobs(); } } g_knobs_init; }
-const Knobs& knobs() { return g_knobs; }
-
-static std::atomic<uint64_t> g_form_hits[FORM_COUNT];
-void form_hit(Form f) { g_form_hits[f].fetch_add(1, std::memory_order_relaxed); }
-static const char* const g_form_names[FORM_COUNT] = {
-    "attn_flash", "attn_row_split", "attn_kv_wide", "attn_kv_narrow", "attn_fused_qkv_wide", "attn_fused_qkv_narrow",
-    "attn_split_reduce", "w4_wgsplit", "w4_ldsa", "w4_tilep", "w4_slabs", "w4_slabs_lds", "w4_slabs_tile", "w4_rowsum",
-    "moe_expert_major", "moe_inline_align", "moe_block16", "moe_tile64", "moe_tile32", "moe_tile_big", "moe_merge_route", "route_split",
-    "route_fused", "route_gemm", "dense_slab_chain", "graph_capture", "graph_replay", "tp_allreduce_rccl",
-    "tp_allreduce_loopback", "tp_allreduce_oneshot", "f16_dense_linear", "w4_fused_tail", "attn_resident", "w4_big", "gather_columns",
-    "perm_producer", "moe_expert_major_pair", "decode_chain", "moe_deferred_merge", "dense_chain", "tp_allreduce_norm_fused", "chain_attn_kv_splits", "chain_qkv_wide", "route_gemm_topk",
-    "moe_pair_rank_lists"};
-const char* form_name(int f) { return f >= 0 && f < FORM_COUNT ? g_form_names[f] : nullptr; }
 }  // namespace fh
 
 using namespace fh;
-
-struct FerrumHipWorkspace {
-    float* ptr = nullptr;
-    size_t bytes = 0;
-};
-
-struct FerrumHipGptq {
-    W4Device dev;
-    bool symmetric = true;
-    __half* gather_scratch = nullptr;   // act-order input gather buffer [m_cap, K]
-    int gather_rows = 0;
-    std::vector<void*> retired_scratch;  // outgrown gather buffers: a graph captured earlier may still hold them → freed with the handle
-    // gemm_phase_batched: rotating (pinned host, device, event) slots for the per-call dispatch arrays
-    struct DispatchSlot { int32_t* host = nullptr; int32_t* dev = nullptr; size_t cap = 0; hipEvent_t done = nullptr; };
-    DispatchSlot slots[4];
-    int next_slot = 0;
-    // expert_major_pair: [2][E] arrival counters + the give-up word of the merged gate_up → down launch
-    unsigned* pair_arrive = nullptr;
-    int pair_experts = 0;
-};
 
 struct FerrumHipGraph {
     hipGraph_t graph = nullptr;
     hipGraphExec_t exec = nullptr;
 };
-
-#define H(p) reinterpret_cast<__half*>(p)
-#define CH(p) reinterpret_cast<const __half*>(p)
-#define ST(s) reinterpret_cast<hipStream_t>(s)
 
 extern "C" {
 
@@ -131,13 +42,10 @@ int ferrum_hip_debug_form_count(void) { return fh::FORM_COUNT; }
 const char* ferrum_hip_debug_form_name(int form) { return fh::form_name(form); }
 int ferrum_hip_debug_form_hits(uint64_t* hits, int capacity) {
     FH_REQUIRE(hits && capacity >= fh::FORM_COUNT, "debug_form_hits: need room for %d counters", (int)fh::FORM_COUNT);
-    for (int i = 0; i < fh::FORM_COUNT; i++) hits[i] = fh::g_form_hits[i].load(std::memory_order_relaxed);
+    fh::form_hits_snapshot(hits);
     return 0;
 }
-int ferrum_hip_debug_form_reset(void) {
-    for (int i = 0; i < fh::FORM_COUNT; i++) fh::g_form_hits[i].store(0, std::memory_order_relaxed);
-    return 0;
-}
+int ferrum_hip_debug_form_reset(void) { fh::form_hits_reset(); return 0; }
 int ferrum_hip_debug_reload_knobs(void) { fh::reload_knobs(); return 0; }
 
 int ferrum_hip_device_count(int* count) {
@@ -330,304 +238,6 @@ int ferrum_hip_gemm_f16t_f32out(const void* a, const void* b, float* out, int m,
     return f16t_gemm_f32out(CH(a), CH(b), out, m, n, k, ws ? ws->ptr : nullptr, ws ? ws->bytes : 0, ST(stream));
 }
 
-// ── GPTQ ────────────────────────────────────────────────────────────────────
-static int upload(const void* host, size_t bytes, void** dev) {
-    *dev = nullptr;
-    if (!bytes) return 0;
-    FH_CHECK_HIP(hipMalloc(dev, bytes));
-    FH_CHECK_HIP(hipMemcpy(*dev, host, bytes, hipMemcpyHostToDevice));
-    return 0;
-}
-
-static int check_gptq_args(int bits, int group_size, int k, int n) {
-    if (bits != 4) { fh::set_error("gptq: only bits=4 supported (got %d)", bits); return FERRUM_HIP_UNSUPPORTED; }
-    if (k <= 0 || n <= 0 || k % 128 != 0 || n % 8 != 0) {
-        fh::set_error("gptq: unsupported shape K=%d N=%d (K %% 128, N %% 8 required)", k, n);
-        return FERRUM_HIP_UNSUPPORTED;
-    }
-    if (group_size <= 0 || group_size % 128 != 0 || k % group_size != 0) {
-        fh::set_error("gptq: unsupported group_size=%d for K=%d (multiple of 128 required)", group_size, k);
-        return FERRUM_HIP_UNSUPPORTED;
-    }
-    return 0;
-}
-
-int ferrum_hip_gptq_load(FerrumHipGptq** handle, const int32_t* qweight, const float* scales, const int32_t* qzeros,
-                         const int32_t* g_idx, const float* bias, int bits, int group_size, int k, int n) {
-    FH_REQUIRE(handle && qweight && scales && qzeros, "gptq_load: null argument");
-    if (int rc = check_gptq_args(bits, group_size, k, n)) return rc;
-    W4HostPacked hp;
-    if (int rc = w4_repack_host(qweight, scales, qzeros, g_idx, nullptr, group_size, k, n, &hp)) return rc;
-    auto* g = new FerrumHipGptq();
-    g->symmetric = hp.symmetric;
-    g->dev.k = k; g->dev.n = n; g->dev.n64 = hp.n64; g->dev.G = hp.G; g->dev.num_experts = 1;
-    int rc = upload(hp.qw.data(), hp.qw.size() * 4, (void**)&g->dev.qw);
-    if (!rc) rc = upload(hp.sc.data(), hp.sc.size() * 2, (void**)&g->dev.sc);
-    if (!rc && !hp.symmetric) rc = upload(hp.zp.data(), hp.zp.size() * 2, (void**)&g->dev.zp);
-    if (!rc && !hp.perm.empty()) rc = upload(hp.perm.data(), hp.perm.size() * 4, (void**)&g->dev.perm);
-    if (!rc && bias) {
-        std::vector<uint16_t> bh(n);
-        for (int i = 0; i < n; i++) { _Float16 h = (_Float16)bias[i]; memcpy(&bh[i], &h, 2); }
-        rc = upload(bh.data(), bh.size() * 2, (void**)&g->dev.bias);
-    }
-    if (rc) { ferrum_hip_gptq_free(g); return rc; }
-    *handle = g;
-    return 0;
-}
-
-int ferrum_hip_gptq_load_stacked(FerrumHipGptq** handle, const int32_t* const* qweights, const float* const* scales,
-                                 const int32_t* const* qzeros, const int32_t* g_idx, int bits, int group_size, int k,
-                                 int n_per_expert, int num_experts, int fuse_gate_up) {
-    FH_REQUIRE(handle && qweights && scales && qzeros && num_experts > 0, "gptq_load_stacked: null argument");
-    if (int rc = check_gptq_args(bits, group_size, k, n_per_expert)) return rc;
-    const int n = n_per_expert;
-    std::vector<int32_t> col_perm;
-    if (fuse_gate_up) {
-        if (n % 64 != 0) { fh::set_error("gptq_load_stacked: fused gate_up needs N %% 64 == 0 (N=%d)", n); return FERRUM_HIP_UNSUPPORTED; }
-        // supertile st = [gate 32st..32st+31 | up I+32st..I+32st+31]
-        const int I = n / 2;
-        col_perm.resize(n);
-        for (int st = 0; st < n / 64; st++)
-            for (int c = 0; c < 64; c++) col_perm[st * 64 + c] = c < 32 ? st * 32 + c : I + st * 32 + (c - 32);
-    }
-    auto* g = new FerrumHipGptq();
-    g->dev.k = k; g->dev.n = n; g->dev.num_experts = num_experts; g->dev.fused_gate_up = fuse_gate_up != 0;
-    std::vector<uint32_t> all_qw;
-    std::vector<uint16_t> all_sc, all_zp;
-    bool any_asym = false;
-    std::vector<W4HostPacked> packed(num_experts);
-    for (int e = 0; e < num_experts; e++) {
-        // one g_idx for the whole stack (capabilities.rs:180-189; cuda/quant.rs:862 ff. samples expert 0's): act-order rows
-        // are packed in sorted-group order and the phase entry points gather the input columns to match
-        if (int rc = w4_repack_host(qweights[e], scales[e], qzeros[e], g_idx, fuse_gate_up ? col_perm.data() : nullptr,
-                                    group_size, k, n, &packed[e])) { delete g; return rc; }
-        any_asym |= !packed[e].symmetric;
-    }
-    g->symmetric = !any_asym;
-    g->dev.n64 = packed[0].n64; g->dev.G = packed[0].G;
-    for (int e = 0; e < num_experts; e++) {
-        all_qw.insert(all_qw.end(), packed[e].qw.begin(), packed[e].qw.end());
-        all_sc.insert(all_sc.end(), packed[e].sc.begin(), packed[e].sc.end());
-        if (any_asym) {
-            if (packed[e].symmetric) {   // materialise zero point 8
-                _Float16 h8 = (_Float16)8.0f; uint16_t u; memcpy(&u, &h8, 2);
-                all_zp.insert(all_zp.end(), packed[e].sc.size(), u);
-            } else {
-                all_zp.insert(all_zp.end(), packed[e].zp.begin(), packed[e].zp.end());
-            }
-        }
-    }
-    int rc = upload(all_qw.data(), all_qw.size() * 4, (void**)&g->dev.qw);
-    if (!rc) rc = upload(all_sc.data(), all_sc.size() * 2, (void**)&g->dev.sc);
-    if (!rc && any_asym) rc = upload(all_zp.data(), all_zp.size() * 2, (void**)&g->dev.zp);
-    if (!rc && !packed[0].perm.empty()) rc = upload(packed[0].perm.data(), packed[0].perm.size() * 4, (void**)&g->dev.perm);
-    if (rc) { ferrum_hip_gptq_free(g); return rc; }
-    *handle = g;
-    return 0;
-}
-
-// Act-order stack: the phase entry points read gathered input rows x'[r][j] = x[r][perm[j]] (`rows` input rows of K columns).
-// The scratch grows outside of graph capture only; an outgrown buffer stays alive with the handle (a captured graph may hold it).
-static int stack_input(const FerrumHipGptq* stack, const void* input, int rows, hipStream_t s, const __half** x) {
-    *x = CH(input);
-    if (!stack->dev.perm || rows <= 0) return 0;
-    auto* g = const_cast<FerrumHipGptq*>(stack);
-    if (g->gather_rows < rows) {
-        if (g->gather_scratch) g->retired_scratch.push_back(g->gather_scratch);
-        g->gather_scratch = nullptr;
-        FH_CHECK_HIP(hipMalloc((void**)&g->gather_scratch, (size_t)rows * g->dev.k * 2));
-        g->gather_rows = rows;
-    }
-    if (int rc = gather_columns_f16(CH(input), g->dev.perm, g->gather_scratch, rows, g->dev.k, s)) return rc;
-    *x = g->gather_scratch;
-    return 0;
-}
-static inline int input_rows(int prob_m, int top_k) { return (prob_m + top_k - 1) / top_k; }      // pair p reads row p / top_k
-
-int ferrum_hip_gptq_free(FerrumHipGptq* g) {
-    if (!g) return 0;
-    if (g->dev.qw) (void)hipFree(g->dev.qw);
-    if (g->dev.sc) (void)hipFree(g->dev.sc);
-    if (g->dev.zp) (void)hipFree(g->dev.zp);
-    if (g->dev.perm) (void)hipFree(g->dev.perm);
-    if (g->dev.bias) (void)hipFree(g->dev.bias);
-    if (g->gather_scratch) (void)hipFree(g->gather_scratch);
-    for (void* p : g->retired_scratch) (void)hipFree(p);
-    if (g->pair_arrive) (void)hipFree(g->pair_arrive);
-    for (auto& sl : g->slots) {
-        if (sl.done) { (void)hipEventSynchronize(sl.done); (void)hipEventDestroy(sl.done); }
-        if (sl.host) (void)hipHostFree(sl.host);
-        if (sl.dev) (void)hipFree(sl.dev);
-    }
-    delete g;
-    return 0;
-}
-
-int ferrum_hip_gptq_info(const FerrumHipGptq* g, int* k, int* n, int* num_experts, int* symmetric) {
-    FH_REQUIRE(g, "gptq_info: null handle");
-    if (k) *k = g->dev.k;
-    if (n) *n = g->dev.n;
-    if (num_experts) *num_experts = g->dev.num_experts;
-    if (symmetric) *symmetric = g->symmetric ? 1 : 0;
-    return 0;
-}
-
-int ferrum_hip_gptq_linear_forward_f16(const FerrumHipGptq* handle, const void* in, void* out, int m,
-                                       FerrumHipWorkspace* ws, void* stream) {
-    FH_REQUIRE(handle && (m == 0 || (in && out)), "gptq_linear_forward: null argument");
-    FH_REQUIRE(handle->dev.num_experts == 1, "gptq_linear_forward: handle is an expert stack");
-    auto* g = const_cast<FerrumHipGptq*>(handle);
-    const __half* x = CH(in);
-    if (g->dev.perm) {
-        // act-order: gather input columns first (cuda/quant.rs:434).  The scratch grows outside
-        // of graph capture only (first call with a larger m); the outgrown buffer stays allocated until the handle is
-        // freed, because a graph captured at the smaller m holds its address.
-        if (g->gather_rows < m) {
-            if (g->gather_scratch) g->retired_scratch.push_back(g->gather_scratch);
-            g->gather_scratch = nullptr;
-            FH_CHECK_HIP(hipMalloc((void**)&g->gather_scratch, (size_t)m * g->dev.k * 2));
-            g->gather_rows = m;
-        }
-        if (int rc = gather_columns_f16(x, g->dev.perm, g->gather_scratch, m, g->dev.k, ST(stream))) return rc;
-        x = g->gather_scratch;
-    }
-    // the bias (if any) is added in the GEMM epilogue / split-K reduce (W4Device::bias)
-    return w4_gemm_dense(g->dev, x, H(out), m, ws ? ws->ptr : nullptr, ws ? ws->bytes : 0, ST(stream));
-}
-
-// op-level entries of the forms only the runner reaches: the fp32 slab producers and the fused combine + add + norm prologue
-int ferrum_hip_gptq_linear_slabs_f16(const FerrumHipGptq* handle, const void* x, float* slabs, size_t slab_bytes, int m, int form,
-                                     int* S_inout, int* rows_pad_out, int* n_pad_out, void* stream) {
-    FH_REQUIRE(handle && S_inout && rows_pad_out && n_pad_out && (m == 0 || (x && slabs)), "gptq_linear_slabs: null argument");
-    FH_REQUIRE(form >= 0 && form <= 2, "gptq_linear_slabs: unknown form %d (0 skinny, 1 LDS-shared activations, 2 64-row tiles)", form);
-    const W4Device& w = handle->dev;
-    FH_REQUIRE(w.num_experts == 1 && w.qw && !w.f16t, "gptq_linear_slabs: handle is not a single INT4 projection");
-    FH_REQUIRE(!w.perm, "gptq_linear_slabs: act-order weights (the runner's producers write the gathered rows themselves)");
-    if (form == 0) {
-        const int S = std::max(1, std::min(*S_inout, w.G));       // the clamp w4_gemm_dense_slabs applies
-        if (int rc = w4_gemm_dense_slabs(w, CH(x), slabs, slab_bytes, m, S, rows_pad_out, n_pad_out, ST(stream))) return rc;
-        *S_inout = S;
-        return 0;
-    }
-    if (form == 1) return w4_gemm_dense_slabs_lds(w, CH(x), slabs, slab_bytes, m, S_inout, rows_pad_out, n_pad_out, ST(stream));
-    return w4_gemm_dense_slabs_tile(w, CH(x), slabs, slab_bytes, m, S_inout, rows_pad_out, n_pad_out, ST(stream));
-}
-
-int ferrum_hip_gptq_linear_forward_fused_tail_f16(const FerrumHipGptq* handle, const void* down, const float* weights,
-                                                  const void* residual_in, void* residual_out, const void* ln_w, float eps, int top_k,
-                                                  void* out, int m, FerrumHipWorkspace* ws, void* stream) {
-    FH_REQUIRE(handle && (m == 0 || (down && weights && residual_in && residual_out && ln_w && out)), "gptq_linear_forward_fused_tail: null argument");
-    FH_REQUIRE(m == 0 || residual_in != residual_out, "gptq_linear_forward_fused_tail: residual_in == residual_out (every workgroup reads, one writes)");
-    FH_REQUIRE(handle->dev.num_experts == 1, "gptq_linear_forward_fused_tail: handle is an expert stack");
-    const FusedCombineNorm fa{CH(down), weights, CH(residual_in), H(residual_out), CH(ln_w), eps, top_k};
-    return w4_gemm_dense(handle->dev, nullptr, H(out), m, ws ? ws->ptr : nullptr, ws ? ws->bytes : 0, ST(stream), &fa);
-}
-
-int ferrum_hip_gptq_linear_can_fuse_tail(const FerrumHipGptq* handle, int m) {
-    return handle && handle->dev.num_experts == 1 && w4_gemm_dense_can_fuse_combine_norm(handle->dev, m) ? 1 : 0;
-}
-
-int ferrum_hip_moe_gemm_phase_f16(const FerrumHipGptq* stack, const void* input, const int32_t* sorted_token_ids,
-                                  const int32_t* expert_ids, const int32_t* num_tokens_past_padded, void* output,
-                                  int prob_m, int moe_block_size, int top_k, int max_blocks, int fused_silu_mul,
-                                  void* stream) {
-    FH_REQUIRE(stack && input && sorted_token_ids && expert_ids && num_tokens_past_padded && output,
-               "moe_gemm_phase: null argument");
-    if (moe_block_size != 16 && moe_block_size != 32 && moe_block_size != 64 && moe_block_size != 96 && moe_block_size != 128) {
-        fh::set_error("moe_gemm_phase: moe_block_size=%d unsupported (16, 32, 64, 96 or 128)", moe_block_size);
-        return FERRUM_HIP_UNSUPPORTED;
-    }
-    if (moe_block_size >= 96 && stack->dev.G % 2 != 0) {
-        fh::set_error("moe_gemm_phase: 96- / 128-row blocks need an even number of 128-wide quant groups (K=%d)", stack->dev.k);
-        return FERRUM_HIP_UNSUPPORTED;
-    }
-    FH_REQUIRE(top_k >= 1, "moe_gemm_phase: top_k=%d", top_k);
-    FH_REQUIRE(!fused_silu_mul || stack->dev.fused_gate_up, "moe_gemm_phase: fused epilogue needs a stack loaded with fuse_gate_up");
-    FH_REQUIRE(fused_silu_mul || !stack->dev.fused_gate_up, "moe_gemm_phase: stack was loaded with fuse_gate_up; plain output is column-permuted");
-    const __half* x = nullptr;
-    if (int rc = stack_input(stack, input, input_rows(prob_m, top_k), ST(stream), &x)) return rc;
-    if (moe_block_size >= 32)   // prefill-sized batches: 128-, 64- or 32-row LDS tiles
-        return w4_gemm_moe_tile(stack->dev, x, H(output), sorted_token_ids, expert_ids, num_tokens_past_padded, prob_m,
-                                max_blocks, moe_block_size, top_k, fused_silu_mul, ST(stream));
-    return w4_gemm_moe(stack->dev, x, H(output), sorted_token_ids, expert_ids, num_tokens_past_padded, prob_m,
-                       max_blocks, top_k, fused_silu_mul, ST(stream));
-}
-
-int ferrum_hip_moe_gemm_phase_inline_align_f16(const FerrumHipGptq* stack, const void* input,
-                                               const int32_t* expert_ids_per_pair, void* output, int prob_m,
-                                               int num_experts, int top_k, int max_blocks, int fused_silu_mul,
-                                               void* stream) {
-    FH_REQUIRE(stack && input && expert_ids_per_pair && output, "moe_gemm_phase_inline_align: null argument");
-    FH_REQUIRE(top_k >= 1, "moe_gemm_phase_inline_align: top_k=%d", top_k);
-    FH_REQUIRE(!fused_silu_mul || stack->dev.fused_gate_up, "moe_gemm_phase_inline_align: fused epilogue needs a stack loaded with fuse_gate_up");
-    FH_REQUIRE(fused_silu_mul || !stack->dev.fused_gate_up, "moe_gemm_phase_inline_align: stack was loaded with fuse_gate_up; plain output is column-permuted");
-    if (prob_m > 1024) { fh::set_error("moe_gemm_phase_inline_align: prob_m=%d > 1024 (use moe_align_block_size + moe_gemm_phase)", prob_m); return FERRUM_HIP_UNSUPPORTED; }
-    const __half* x = nullptr;
-    if (int rc = stack_input(stack, input, input_rows(prob_m, top_k), ST(stream), &x)) return rc;
-    return w4_gemm_moe_inline_align(stack->dev, x, H(output), expert_ids_per_pair, num_experts, prob_m, max_blocks,
-                                    top_k, fused_silu_mul, nullptr, nullptr, nullptr, ST(stream));
-}
-
-int ferrum_hip_moe_gemm_phase_expert_major_f16(const FerrumHipGptq* stack, const void* input,
-                                               const int32_t* expert_ids_per_pair, void* output, int prob_m,
-                                               int num_experts, int top_k, int fused_silu_mul, void* stream) {
-    FH_REQUIRE(stack && input && expert_ids_per_pair && output, "moe_gemm_phase_expert_major: null argument");
-    FH_REQUIRE(top_k >= 1 && num_experts >= 1, "moe_gemm_phase_expert_major: top_k=%d num_experts=%d", top_k, num_experts);
-    FH_REQUIRE(!fused_silu_mul || stack->dev.fused_gate_up, "moe_gemm_phase_expert_major: fused epilogue needs a stack loaded with fuse_gate_up");
-    FH_REQUIRE(fused_silu_mul || !stack->dev.fused_gate_up, "moe_gemm_phase_expert_major: stack was loaded with fuse_gate_up; plain output is column-permuted");
-    if (prob_m > 1024) { fh::set_error("moe_gemm_phase_expert_major: prob_m=%d > 1024 (use moe_align_block_size + moe_gemm_phase)", prob_m); return FERRUM_HIP_UNSUPPORTED; }
-    const __half* x = nullptr;
-    if (int rc = stack_input(stack, input, input_rows(prob_m, top_k), ST(stream), &x)) return rc;
-    return w4_gemm_moe_expert_major(stack->dev, x, H(output), expert_ids_per_pair, num_experts, prob_m, top_k,
-                                    fused_silu_mul, ST(stream));
-}
-
-int ferrum_hip_moe_gemm_phase_expert_major_pair_f16(FerrumHipGptq* gate_up_stack, const FerrumHipGptq* down_stack, const void* input,
-                                                    const int32_t* expert_ids_per_pair, void* act_out, void* output, int prob_m,
-                                                    int num_experts, int top_k, void* stream) {
-    FH_REQUIRE(gate_up_stack && down_stack && input && expert_ids_per_pair && act_out && output, "moe_gemm_phase_expert_major_pair: null argument");
-    FH_REQUIRE(top_k >= 1 && num_experts >= 1, "moe_gemm_phase_expert_major_pair: top_k=%d num_experts=%d", top_k, num_experts);
-    FH_REQUIRE(gate_up_stack->dev.fused_gate_up && !down_stack->dev.fused_gate_up,
-               "moe_gemm_phase_expert_major_pair: gate_up stack must be loaded with fuse_gate_up, the down stack without");
-    if (prob_m > 1024) { fh::set_error("moe_gemm_phase_expert_major_pair: prob_m=%d > 1024", prob_m); return FERRUM_HIP_UNSUPPORTED; }
-    if (down_stack->dev.perm) {       // the gated activations would need a gather between the two GEMMs of the launch
-        fh::set_error("moe_gemm_phase_expert_major_pair: act-order down stack (run the two phases separately)");
-        return FERRUM_HIP_UNSUPPORTED;
-    }
-    const __half* x_in = nullptr;
-    if (int rc = stack_input(gate_up_stack, input, input_rows(prob_m, top_k), ST(stream), &x_in)) return rc;
-    FerrumHipGptq* g = gate_up_stack;
-    if (g->pair_experts < num_experts) {
-        // (a captured graph may still hold the old counters: retired with the handle, like outgrown gather buffers)
-        if (g->pair_arrive) g->retired_scratch.push_back(g->pair_arrive);
-        g->pair_arrive = nullptr;
-        const size_t words = (size_t)2 * num_experts * MOE_PAIR_COUNTER_STRIDE + 4;
-        FH_CHECK_HIP(hipMalloc((void**)&g->pair_arrive, words * sizeof(unsigned)));
-        FH_CHECK_HIP(hipMemset(g->pair_arrive, 0, words * sizeof(unsigned)));
-        g->pair_experts = num_experts;
-    }
-    // op level: the counters are zeroed by a memset node in front of every launch (a captured call replays with the same
-    // pointers, so the runner's alternating halves do not apply); the give-up word is checked by ferrum_hip_moe_pair_status
-    unsigned* arrive = g->pair_arrive;
-    const size_t half = (size_t)g->pair_experts * MOE_PAIR_COUNTER_STRIDE;
-    FH_CHECK_HIP(hipMemsetAsync(arrive, 0, half * sizeof(unsigned), ST(stream)));
-    int took = 0;
-    if (int rc = w4_gemm_moe_expert_major_pair(g->dev, down_stack->dev, x_in, H(act_out), H(output), expert_ids_per_pair, num_experts,
-                                               prob_m, top_k, arrive, arrive + half, arrive + 2 * half, &took, ST(stream)))
-        return rc;
-    if (!took) { fh::set_error("moe_gemm_phase_expert_major_pair: shapes not taken by the merged form"); return FERRUM_HIP_UNSUPPORTED; }
-    return 0;
-}
-
-/* number of in-launch waits of the stack's merged launches that gave up so far (0 = every hand-off completed) */
-int ferrum_hip_moe_pair_status(const FerrumHipGptq* gate_up_stack, unsigned* timeouts) {
-    FH_REQUIRE(gate_up_stack && timeouts, "moe_pair_status: null argument");
-    *timeouts = 0;
-    if (!gate_up_stack->pair_arrive) return 0;
-    FH_CHECK_HIP(hipMemcpy(timeouts, gate_up_stack->pair_arrive + 2 * (size_t)gate_up_stack->pair_experts * MOE_PAIR_COUNTER_STRIDE, sizeof(unsigned), hipMemcpyDeviceToHost));
-    return 0;
-}
-
 int ferrum_hip_sandwich_add_rms_norm_f32(const void* branch_f16, const void* w_branch, float* residual_f32, const void* w_next,
                                          float eps, void* norm_out_f16, int tokens, int dim, void* stream) {
     FH_REQUIRE(tokens == 0 || (branch_f16 && w_branch && residual_f32 && (!w_next || norm_out_f16)), "sandwich_add_rms_norm_f32: null buffer");
@@ -748,9 +358,6 @@ int ferrum_hip_paged_batched_decode_attention_f16(const void* q, const void* k_p
 // BackendPagedKv::paged_decode_attention (traits.rs:1719-1738).  q_len == 1: q / out [num_seqs, num_heads, head_dim]
 // token-major, one query token per sequence.  q_len > 1: ONE sequence in causal prefill, q / out [num_heads, q_len, head_dim]
 // head-major; context_lens[0] is the FINAL kv length (token i sees positions [0, context_len − q_len + 1 + i)).
-__global__ void single_seq_index_kernel(const uint32_t* __restrict__ context_lens, uint32_t* __restrict__ cu, uint32_t* __restrict__ pos, int q_len) {
-    if (threadIdx.x == 0) { cu[0] = 0; cu[1] = (uint32_t)q_len; pos[0] = context_lens[0] - (uint32_t)q_len; }
-}
 int ferrum_hip_paged_decode_attention_f16(const void* q, const void* k_pool, const void* v_pool, void* out,
                                           const int32_t* block_tables, const uint32_t* context_lens, int num_seqs, int num_heads,
                                           int num_kv_heads, int head_dim, int block_size, int max_num_blocks_per_seq, int q_len,
@@ -764,21 +371,9 @@ int ferrum_hip_paged_decode_attention_f16(const void* q, const void* k_pool, con
                                                   num_heads, num_kv_heads, head_dim, block_size, max_num_blocks_per_seq,
                                                   ws ? ws->ptr : nullptr, ws ? ws->bytes : 0, ST(stream));
     if (num_seqs != 1) { fh::set_error("paged_decode_attention: q_len=%d > 1 is the single-sequence prefill form (num_seqs=%d)", q_len, num_seqs); return FERRUM_HIP_UNSUPPORTED; }
-    const size_t elems = (size_t)q_len * num_heads * head_dim;
-    const size_t need = 2 * elems * 2 + 256;
-    FH_REQUIRE(ws && ws->ptr && ws->bytes >= need + (1 << 20), "paged_decode_attention: workspace of %zu bytes needed for the head-major transposes", need + (1 << 20));
-    __half* q_tm = reinterpret_cast<__half*>(ws->ptr);
-    __half* o_tm = q_tm + elems;
-    uint32_t* idx = reinterpret_cast<uint32_t*>(o_tm + elems);
-    float* attn_ws = reinterpret_cast<float*>(reinterpret_cast<uint8_t*>(ws->ptr) + (need + 255) / 256 * 256);
-    const size_t attn_ws_bytes = ws->bytes - (need + 255) / 256 * 256;
-    hipLaunchKernelGGL(single_seq_index_kernel, dim3(1), dim3(64), 0, ST(stream), context_lens, idx, idx + 2, q_len);
-    FH_CHECK_LAUNCH();
-    if (int rc = transpose_head_to_token_f16(CH(q), q_tm, q_len, num_heads, head_dim, ST(stream))) return rc;
-    if (int rc = paged_varlen_attention_f16(q_tm, CH(k_pool), CH(v_pool), o_tm, idx, idx + 2, block_tables, 1, q_len, q_len, kv_bound,
-                                            num_heads, num_kv_heads, head_dim, 0, block_size, max_num_blocks_per_seq, attn_ws,
-                                            attn_ws_bytes, ST(stream))) return rc;
-    return transpose_token_to_head_f16(o_tm, H(out), q_len, num_heads, head_dim, ST(stream));
+    return paged_single_seq_prefill_attention_f16(CH(q), CH(k_pool), CH(v_pool), H(out), block_tables, context_lens, q_len, num_heads,
+                                                  num_kv_heads, head_dim, block_size, max_num_blocks_per_seq, ws ? ws->ptr : nullptr,
+                                                  ws ? ws->bytes : 0, ST(stream));
 }
 
 // BackendGraph (capabilities.rs:35-70): begin / end stream capture, replay, drop.  The key → graph map of the trait
@@ -893,77 +488,6 @@ int ferrum_hip_weighted_sum_batched_f16(const void* slots, const float* weights,
     return moe_combine_f16(CH(slots), weights + weights_offset, H(out) + out_offset, batch, top_k, hidden, 0, ST(stream));
 }
 
-// MarlinExpertStack::gemm_phase_batched (marlin_expert_stack.rs:63-74): dispatches[i] = (expert, in_row_offset,
-// out_row_offset, m); rows [in_off, in_off + m) of `input` × tile[expert] → rows [out_off, out_off + m) of `output`.
-// One grouped launch per distinct (out_off − in_off): the dispatch list becomes the block-major routing arrays of the
-// grouped GEMM (16-row blocks, or 64-row LDS tiles when the experts see ≥ 32 rows on average).
-int ferrum_hip_moe_gemm_phase_batched_f16(FerrumHipGptq* stack, const void* input, const int32_t* dispatches, int num_dispatches,
-                                          void* output, int k, int fused_silu_mul, void* stream) {
-    FH_REQUIRE(stack && (num_dispatches == 0 || (input && dispatches && output)), "gemm_phase_batched: null argument");
-    FH_REQUIRE(k == stack->dev.k, "gemm_phase_batched: k=%d but the stack was packed with K=%d", k, stack->dev.k);
-    FH_REQUIRE(!fused_silu_mul || stack->dev.fused_gate_up, "gemm_phase_batched: fused epilogue needs a stack loaded with fuse_gate_up");
-    FH_REQUIRE(fused_silu_mul || !stack->dev.fused_gate_up, "gemm_phase_batched: stack was loaded with fuse_gate_up; plain output is column-permuted");
-    if (num_dispatches <= 0) return 0;
-    long rows = 0, max_row = 0;
-    for (int i = 0; i < num_dispatches; i++) {
-        const int32_t* d = dispatches + 4 * i;
-        FH_REQUIRE(d[0] >= 0 && d[0] < stack->dev.num_experts && d[1] >= 0 && d[2] >= 0 && d[3] >= 0,
-                   "gemm_phase_batched: dispatch %d = (%d, %d, %d, %d) out of range", i, d[0], d[1], d[2], d[3]);
-        rows += d[3];
-        max_row = std::max<long>(max_row, (long)d[1] + d[3]);
-    }
-    if (rows == 0) return 0;
-    const int br = rows >= 32L * num_dispatches ? 64 : 16;
-    // group by output displacement (normally one group: in_off == out_off, the packed-row convention)
-    std::vector<long> deltas;
-    for (int i = 0; i < num_dispatches; i++) {
-        const long dl = (long)dispatches[4 * i + 2] - dispatches[4 * i + 1];
-        if (dispatches[4 * i + 3] > 0 && std::find(deltas.begin(), deltas.end(), dl) == deltas.end()) deltas.push_back(dl);
-    }
-    const int ldo = fused_silu_mul ? stack->dev.n / 2 : stack->dev.n;
-    const __half* x_in = nullptr;
-    if (int rc = stack_input(stack, input, (int)max_row, ST(stream), &x_in)) return rc;
-    for (long dl : deltas) {
-        std::vector<int32_t> sorted, blocks;
-        for (int i = 0; i < num_dispatches; i++) {
-            const int32_t* d = dispatches + 4 * i;
-            if (d[3] == 0 || (long)d[2] - d[1] != dl) continue;
-            for (int r0 = 0; r0 < d[3]; r0 += br) {
-                blocks.push_back(d[0]);
-                for (int r = 0; r < br; r++) sorted.push_back(r0 + r < d[3] ? d[1] + r0 + r : (int32_t)max_row);   // sentinel = prob_m
-            }
-        }
-        const size_t nb = blocks.size(), need = sorted.size() + nb + 4;
-        FerrumHipGptq::DispatchSlot& sl = stack->slots[stack->next_slot];
-        stack->next_slot = (stack->next_slot + 1) % 4;
-        if (sl.done) FH_CHECK_HIP(hipEventSynchronize(sl.done));      // the launch that last used this slot has consumed it
-        else FH_CHECK_HIP(hipEventCreateWithFlags(&sl.done, hipEventDisableTiming));
-        if (sl.cap < need) {
-            if (sl.host) (void)hipHostFree(sl.host);
-            if (sl.dev) (void)hipFree(sl.dev);
-            sl.host = nullptr; sl.dev = nullptr; sl.cap = 0;
-            FH_CHECK_HIP(hipHostMalloc((void**)&sl.host, need * 2 * 4, hipHostMallocDefault));
-            FH_CHECK_HIP(hipMalloc((void**)&sl.dev, need * 2 * 4));
-            sl.cap = need * 2;
-        }
-        memcpy(sl.host, sorted.data(), sorted.size() * 4);
-        memcpy(sl.host + sorted.size(), blocks.data(), nb * 4);
-        sl.host[sorted.size() + nb] = (int32_t)sorted.size();           // total_tokens_post_pad
-        FH_CHECK_HIP(hipMemcpyAsync(sl.dev, sl.host, need * 4, hipMemcpyHostToDevice, ST(stream)));
-        const int32_t* d_sorted = sl.dev;
-        const int32_t* d_blocks = sl.dev + sorted.size();
-        const int32_t* d_total = sl.dev + sorted.size() + nb;
-        __half* out_shift = H(output) + dl * ldo;                        // row (in_off + r) of the shifted view = out_off + r
-        int rc = br == 64 ? w4_gemm_moe_tile(stack->dev, x_in, out_shift, d_sorted, d_blocks, d_total, (int)max_row, (int)nb, 64, 1,
-                                             fused_silu_mul, ST(stream))
-                          : w4_gemm_moe(stack->dev, x_in, out_shift, d_sorted, d_blocks, d_total, (int)max_row, (int)nb, 1,
-                                        fused_silu_mul, ST(stream));
-        if (rc) return rc;
-        FH_CHECK_HIP(hipEventRecord(sl.done, ST(stream)));
-    }
-    return 0;
-}
-
 int ferrum_hip_fused_add_rms_norm_route_f16(void* residual, const void* x, const void* w, float eps, void* norm_out,
                                             const void* router_w, int num_experts, int top_k, int norm_topk_prob,
                                             int32_t* expert_ids, float* expert_weights, float* logits_out, int tokens,
@@ -1007,21 +531,6 @@ int ferrum_hip_fused_add_rms_norm_route_split_f16(const void* residual_in, void*
                                               ld_slab, CH(w), eps, H(norm_out), CH(router_w_tiled), num_experts, top_k,
                                               num_parts, reinterpret_cast<RouteCand*>(cand), stats, arrive, norm_topk_prob,
                                               expert_ids, expert_weights, logits_out, tokens, hidden, ST(stream));
-}
-int ferrum_hip_moe_gemm_phase_merge_route_f16(const FerrumHipGptq* stack, const void* input, const void* cand,
-                                              const float* stats, void* output, int tokens, int num_parts, int top_k,
-                                              int norm_topk_prob, int num_experts, int max_blocks, int fused_silu_mul,
-                                              int32_t* expert_ids_out, float* expert_weights_out,
-                                              int32_t* sorted_token_ids_out, int32_t* block_ids_out,
-                                              int32_t* total_post_pad_out, void* stream) {
-    FH_REQUIRE(stack && input && cand && stats && output && expert_ids_out && expert_weights_out, "merge_route: null argument");
-    FH_REQUIRE(!fused_silu_mul || stack->dev.fused_gate_up, "merge_route: fused epilogue needs a stack loaded with fuse_gate_up");
-    FH_REQUIRE(fused_silu_mul || !stack->dev.fused_gate_up, "merge_route: stack was loaded with fuse_gate_up; plain output is column-permuted");
-    const __half* x_in = nullptr;
-    if (int rc = stack_input(stack, input, tokens, ST(stream), &x_in)) return rc;
-    return w4_gemm_moe_merge_route(stack->dev, x_in, H(output), reinterpret_cast<const RouteCand*>(cand), stats, tokens,
-                                   num_parts, top_k, norm_topk_prob, num_experts, max_blocks, fused_silu_mul, expert_ids_out,
-                                   expert_weights_out, sorted_token_ids_out, block_ids_out, total_post_pad_out, ST(stream));
 }
 
 // ── sampling ────────────────────────────────────────────────────────────────

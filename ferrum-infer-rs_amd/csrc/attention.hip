@@ -1,4 +1,4 @@
-// Paged-KV attention for gfx950: the three entry points.  They check the arguments, fill the kernel argument block, ask
+// Paged-KV attention for gfx950: the three entry points and the head-major single-sequence prefill over them.  They check the arguments, fill the kernel argument block, ask
 // attn_plan.h which form the shape takes and hand the plan to the launch function of the kernel family: attention_decode.hip
 // (KV-split, row-split, fused-qkv decode and the split reduce) or attention_prefill.hip (the LDS-staged prefill forms).
 //
@@ -9,6 +9,11 @@
 #include "attn_common.h"
 #include "kernels.h"
 #include "kv_layout.h"
+
+// index words of the head-major single-sequence prefill below (C linkage: the symbol name it has always had)
+extern "C" __global__ void single_seq_index_kernel(const uint32_t* __restrict__ context_lens, uint32_t* __restrict__ cu, uint32_t* __restrict__ pos, int q_len) {
+    if (threadIdx.x == 0) { cu[0] = 0; cu[1] = (uint32_t)q_len; pos[0] = context_lens[0] - (uint32_t)q_len; }
+}
 
 namespace fh {
 
@@ -100,6 +105,31 @@ int paged_decode_attention_fused_qkv_f16(const __half* qkv, const __half* q_norm
     return paged_attention_launch(nullptr, k_pool, v_pool, out, nullptr, nullptr, valid_kv_lens, block_tables, num_seqs,
                                   num_seqs, 1, max_kv_len, num_heads, num_kv_heads, head_dim, sliding_window, block_size,
                                   max_blocks_per_seq, workspace, workspace_bytes, s, &fq, out_scatter);
+}
+
+// The q_len > 1 form of BackendPagedKv::paged_decode_attention (traits.rs:1719-1738): ONE sequence in causal prefill, q / out
+// [num_heads, q_len, head_dim] head-major; context_lens[0] is the FINAL kv length (token i sees positions
+// [0, context_len − q_len + 1 + i)).  The workspace holds the two token-major copies, the index words and the attention scratch.
+int paged_single_seq_prefill_attention_f16(const __half* q, const __half* k_pool, const __half* v_pool, __half* out,
+                                           const int32_t* block_tables, const uint32_t* context_lens, int q_len, int num_heads,
+                                           int num_kv_heads, int head_dim, int block_size, int max_num_blocks_per_seq,
+                                           float* workspace, size_t workspace_bytes, hipStream_t s) {
+    const int kv_bound = max_num_blocks_per_seq * block_size;            // the kv lengths live on the device: the table width bounds them
+    const size_t elems = (size_t)q_len * num_heads * head_dim;
+    const size_t need = 2 * elems * 2 + 256;
+    FH_REQUIRE(workspace && workspace_bytes >= need + (1 << 20), "paged_decode_attention: workspace of %zu bytes needed for the head-major transposes", need + (1 << 20));
+    __half* q_tm = reinterpret_cast<__half*>(workspace);
+    __half* o_tm = q_tm + elems;
+    uint32_t* idx = reinterpret_cast<uint32_t*>(o_tm + elems);
+    float* attn_ws = reinterpret_cast<float*>(reinterpret_cast<uint8_t*>(workspace) + (need + 255) / 256 * 256);
+    const size_t attn_ws_bytes = workspace_bytes - (need + 255) / 256 * 256;
+    hipLaunchKernelGGL(single_seq_index_kernel, dim3(1), dim3(64), 0, s, context_lens, idx, idx + 2, q_len);
+    FH_CHECK_LAUNCH();
+    if (int rc = transpose_head_to_token_f16(q, q_tm, q_len, num_heads, head_dim, s)) return rc;
+    if (int rc = paged_varlen_attention_f16(q_tm, k_pool, v_pool, o_tm, idx, idx + 2, block_tables, 1, q_len, q_len, kv_bound,
+                                            num_heads, num_kv_heads, head_dim, 0, block_size, max_num_blocks_per_seq, attn_ws,
+                                            attn_ws_bytes, s)) return rc;
+    return transpose_token_to_head_f16(o_tm, out, q_len, num_heads, head_dim, s);
 }
 
 }  // namespace fh

@@ -1,4 +1,4 @@
-// Thread-local error text returned by ferrum_hip_last_error() (abi.cc).  Host-only: no HIP header needed.
+// Thread-local error text returned by ferrum_hip_last_error(); set_error / last_error are defined in abi.cc.  Host-only: no HIP header needed.
 #pragma once
 
 namespace fh {

@@ -182,6 +182,11 @@ int paged_batched_decode_attention_f16(const __half* q, const __half* k_pool, co
                                        int max_kv_len, int num_heads, int num_kv_heads, int head_dim, int block_size,
                                        int max_blocks_per_seq, float* workspace, size_t workspace_bytes,
                                        hipStream_t s, const int32_t* out_scatter = nullptr);
+// q_len > 1 form of paged_decode_attention: one sequence, q / out head-major [num_heads, q_len, head_dim] (attention.hip)
+int paged_single_seq_prefill_attention_f16(const __half* q, const __half* k_pool, const __half* v_pool, __half* out,
+                                           const int32_t* block_tables, const uint32_t* context_lens, int q_len, int num_heads,
+                                           int num_kv_heads, int head_dim, int block_size, int max_num_blocks_per_seq,
+                                           float* workspace, size_t workspace_bytes, hipStream_t s);
 size_t paged_attention_workspace_bytes(int total_q_tokens, int num_heads, int head_dim, int max_kv_len);
 
 // ── whole-block KV moves (kv_move.hip): fork / truncate / host swap ──────────

@@ -6,6 +6,7 @@
 #include "runner.h"
 #include "knobs.h"
 #include "tp_comm.h"
+#include "w4_upload.h"
 
 using namespace fh;
 
@@ -20,52 +21,6 @@ int upload_f32_as_f16(const float* src, size_t n, __half** dst) {
     if (!*dst) FH_CHECK_HIP(hipMalloc((void**)dst, n * 2));
     FH_CHECK_HIP(hipMemcpy(*dst, tmp.data(), n * 2, hipMemcpyHostToDevice));
     return 0;
-}
-
-void free_w4(W4Device& w) {
-    if (w.qw) (void)hipFree(w.qw);
-    if (w.sc) (void)hipFree(w.sc);
-    if (w.zp) (void)hipFree(w.zp);
-    if (w.perm) (void)hipFree(w.perm);
-    if (w.inv_perm) (void)hipFree(w.inv_perm);
-    if (w.bias) (void)hipFree(w.bias);
-    if (w.f16t) (void)hipFree(w.f16t);
-    w = W4Device();
-}
-
-int upload_perm(const std::vector<int32_t>& perm, W4Device* w);
-int upload_w4(const W4HostPacked& hp, W4Device* w) {
-    free_w4(*w);
-    w->k = hp.k; w->n = hp.n; w->n64 = hp.n64; w->G = hp.G; w->num_experts = 1;
-    FH_CHECK_HIP(hipMalloc((void**)&w->qw, hp.qw.size() * 4));
-    FH_CHECK_HIP(hipMemcpy(w->qw, hp.qw.data(), hp.qw.size() * 4, hipMemcpyHostToDevice));
-    FH_CHECK_HIP(hipMalloc((void**)&w->sc, hp.sc.size() * 2));
-    FH_CHECK_HIP(hipMemcpy(w->sc, hp.sc.data(), hp.sc.size() * 2, hipMemcpyHostToDevice));
-    if (!hp.symmetric) {
-        FH_CHECK_HIP(hipMalloc((void**)&w->zp, hp.zp.size() * 2));
-        FH_CHECK_HIP(hipMemcpy(w->zp, hp.zp.data(), hp.zp.size() * 2, hipMemcpyHostToDevice));
-    }
-    return hp.perm.empty() ? 0 : upload_perm(hp.perm, w);
-}
-
-// input-column permutation of an act-order projection and its inverse (producers that scatter use the inverse)
-int upload_perm(const std::vector<int32_t>& perm, W4Device* w) {
-    std::vector<int32_t> inv(perm.size());
-    for (size_t j = 0; j < perm.size(); j++) inv[perm[j]] = (int32_t)j;
-    FH_CHECK_HIP(hipMalloc((void**)&w->perm, perm.size() * 4));
-    FH_CHECK_HIP(hipMemcpy(w->perm, perm.data(), perm.size() * 4, hipMemcpyHostToDevice));
-    FH_CHECK_HIP(hipMalloc((void**)&w->inv_perm, inv.size() * 4));
-    FH_CHECK_HIP(hipMemcpy(w->inv_perm, inv.data(), inv.size() * 4, hipMemcpyHostToDevice));
-    return 0;
-}
-
-// fused gate_up column order: supertile st = [gate 32st.. | up I+32st..]
-std::vector<int32_t> gate_up_col_perm(int n) {
-    std::vector<int32_t> p(n);
-    const int I = n / 2;
-    for (int st = 0; st < n / 64; st++)
-        for (int c = 0; c < 64; c++) p[st * 64 + c] = c < 32 ? st * 32 + c : I + st * 32 + (c - 32);
-    return p;
 }
 
 // RoPE table (llama_family.rs:5220-5282): angle in f64, stored f32.
@@ -224,7 +179,7 @@ int ferrum_hip_model_destroy(FerrumHipModel* m) {
     for (auto& L : m->layers) {
         for (__half* p : {L.input_ln, L.post_ln, L.q_norm, L.k_norm, L.router, L.k_pool, L.v_pool, L.post_attn_ln, L.post_ffn_ln, L.qkv_bias})
             if (p) (void)hipFree(p);
-        free_w4(L.qkv); free_w4(L.o); free_w4(L.gate_up); free_w4(L.down); free_w4(L.exp_gate_up); free_w4(L.exp_down);
+        w4_free(L.qkv); w4_free(L.o); w4_free(L.gate_up); w4_free(L.down); w4_free(L.exp_gate_up); w4_free(L.exp_down);
     }
     for (void* p : {(void*)m->embed, (void*)m->lm_head, (void*)m->lm_head_t, (void*)m->final_norm, (void*)m->cos_t, (void*)m->sin_t,
                     (void*)m->residual, (void*)m->norm_out, (void*)m->qkv_out, (void*)m->q_out, (void*)m->attn_out,
@@ -277,15 +232,6 @@ int ferrum_hip_model_set_layer_dense_f32(FerrumHipModel* m, int layer, int which
     return FERRUM_HIP_INVALID;
 }
 
-static int ensure_expert_stack(W4Device* w, int k, int n, int E, bool fused) {
-    if (w->qw) return 0;
-    w->k = k; w->n = n; w->n64 = (n + 63) / 64; w->G = k / 128; w->num_experts = E; w->fused_gate_up = fused;
-    size_t qw = (size_t)w->n64 * w->G * 4 * 64 * 4, sc = (size_t)w->n64 * w->G * 16 * 4;
-    FH_CHECK_HIP(hipMalloc((void**)&w->qw, qw * 4 * E));
-    FH_CHECK_HIP(hipMalloc((void**)&w->sc, sc * 2 * E));
-    return 0;
-}
-
 // Dense gate_up: when down is act-order (perm P: down reads act'[j] = act[P[j]]), pack column j of the gate half from the
 // checkpoint's gate column P[j] and column I + j from up column I + P[j]: the gated activation of the packed output IS act'.
 static int pack_gate_up(FerrumHipModel* m, LayerWeights& L, const int32_t* qweight, const float* scales, const int32_t* qzeros,
@@ -300,7 +246,7 @@ static int pack_gate_up(FerrumHipModel* m, LayerWeights& L, const int32_t* qweig
         for (int j = 0; j < I; j++) { cols[j] = P[j]; cols[I + j] = I + P[j]; }
     }
     if (int r = w4_repack_host(qweight, scales, qzeros, g_idx, fold ? cols.data() : nullptr, m->cfg.group_size, k, n, &hp)) return r;
-    if (int r = upload_w4(hp, &L.gate_up)) return r;
+    if (int r = w4_upload(hp, &L.gate_up)) return r;
     L.down.perm_folded = fold;
     return 0;
 }
@@ -338,7 +284,7 @@ int ferrum_hip_model_set_gptq(FerrumHipModel* m, int layer, int which, int exper
         }
         if (which == 2) return pack_gate_up(m, L, qweight, scales, qzeros, g_idx, k, n);
         if (int r = w4_repack_host(qweight, scales, qzeros, g_idx, nullptr, c.group_size, k, n, &hp)) return r;
-        if (int r = upload_w4(hp, dst)) return r;
+        if (int r = w4_upload(hp, dst)) return r;
         if (which == 3) {
             L.down_set = true;
             L.down_perm_host = hp.perm;
@@ -364,27 +310,16 @@ int ferrum_hip_model_set_gptq(FerrumHipModel* m, int layer, int which, int exper
     W4Device* w = gu ? &L.exp_gate_up : &L.exp_down;
     std::vector<int32_t>& perm_host = gu ? L.exp_gate_up_perm_host : L.exp_down_perm_host;
     const bool first = L.exp_loaded.empty() || std::none_of(L.exp_loaded.begin(), L.exp_loaded.end(), [&](uint8_t b) { return (b & (gu ? 1 : 2)) != 0; });
-    if (int rc = ensure_expert_stack(w, k, n, m->ep_E, gu)) return rc;
+    if (int rc = w4_stack_reserve(w, k, n, m->ep_E, gu)) return rc;
     if (first) {
         perm_host = hp.perm;
         if (!hp.perm.empty())
-            if (int rc = upload_perm(hp.perm, w)) return rc;
+            if (int rc = w4_upload_perm(hp.perm, w)) return rc;
     } else {
         FH_REQUIRE(perm_host == hp.perm, "model_set_gptq: layer %d expert %d %s brings a different g_idx than the experts before it (a stack shares one)",
                    layer, expert + m->ep_e0, gu ? "gate_up" : "down");
     }
-    // explicit zero points (asymmetric packs; cuda/quant.rs:795-839 sends those to the vLLM MoE lane): the stack gets a zero-point
-    // array as soon as one expert needs it; symmetric experts of such a stack carry the implicit zero 8
-    const size_t sc_elems = hp.sc.size();
-    if (!hp.symmetric && !w->zp) {
-        FH_CHECK_HIP(hipMalloc((void**)&w->zp, sc_elems * 2 * (size_t)m->ep_E));
-        std::vector<uint16_t> eight(sc_elems * (size_t)m->ep_E, (uint16_t)0x4800);          // fp16 8.0
-        FH_CHECK_HIP(hipMemcpy(w->zp, eight.data(), eight.size() * 2, hipMemcpyHostToDevice));
-    }
-    FH_CHECK_HIP(hipMemcpy(w->qw + (size_t)expert * hp.qw.size(), hp.qw.data(), hp.qw.size() * 4, hipMemcpyHostToDevice));
-    FH_CHECK_HIP(hipMemcpy(w->sc + (size_t)expert * hp.sc.size(), hp.sc.data(), hp.sc.size() * 2, hipMemcpyHostToDevice));
-    if (w->zp && !hp.symmetric)
-        FH_CHECK_HIP(hipMemcpy(reinterpret_cast<uint16_t*>(w->zp) + (size_t)expert * sc_elems, hp.zp.data(), sc_elems * 2, hipMemcpyHostToDevice));
+    if (int rc = w4_stack_put(w, expert, hp)) return rc;
     if (L.exp_loaded.empty()) L.exp_loaded.assign(m->ep_E, 0);
     L.exp_loaded[expert] |= gu ? 1 : 2;
     return 0;
@@ -408,8 +343,8 @@ int ferrum_hip_model_set_dense_f32(FerrumHipModel* m, int layer, int which, cons
     }
     if (rc) return rc;
     FH_REQUIRE(k % 32 == 0, "model_set_dense: K=%d must be a multiple of 32", k);
-    free_w4(*dst);
-    dst->k = k; dst->n = n; dst->n64 = (n + 63) / 64; dst->G = k / 128; dst->num_experts = 1;
+    w4_free(*dst);
+    w4_set_dims(dst, k, n, 1, false);
     __half* row = nullptr;
     if (int r = upload_f32_as_f16(weight, (size_t)n * k, &row)) return r;
     hipError_t e = hipMalloc((void**)&dst->f16t, f16t_elems(n, k) * 2);
@@ -429,9 +364,9 @@ static void launch1d(void (*k)(__half*, long, uint64_t, float, float), __half* p
 // dequantised W has std ≈ 1/sqrt(K) and activations stay O(1) through all layers,
 // zero point 8 (sym), norm weights 1, embeddings / lm_head / router N(0, 0.02).
 static int synth_w4(W4Device* w, int k, int n, int E, bool fused, uint64_t seed, hipStream_t s) {
-    free_w4(*w);
-    w->k = k; w->n = n; w->n64 = (n + 63) / 64; w->G = k / 128; w->num_experts = E; w->fused_gate_up = fused;
-    long qw = (long)w->n64 * w->G * 4 * 64 * 4 * E, sc = (long)w->n64 * w->G * 16 * 4 * E;
+    w4_free(*w);
+    w4_set_dims(w, k, n, E, fused);
+    long qw = (long)w4_qw_words(w->n64, w->G) * E, sc = (long)w4_sc_elems(w->n64, w->G) * E;
     FH_CHECK_HIP(hipMalloc((void**)&w->qw, qw * 4));
     FH_CHECK_HIP(hipMalloc((void**)&w->sc, sc * 2));
     hipLaunchKernelGGL(synth_u32_kernel, dim3(cdiv(qw, 256)), dim3(256), 0, s, w->qw, qw, seed);
@@ -503,7 +438,7 @@ int ferrum_hip_model_init_synthetic(FerrumHipModel* m, uint64_t seed) {
                     st = st * 6364136223846793005ull + 1442695040888963407ull;
                     std::swap(perm[i], perm[(int)((st >> 33) % (uint64_t)(i + 1))]);
                 }
-                if (int rc = upload_perm(perm, w)) return rc;
+                if (int rc = w4_upload_perm(perm, w)) return rc;
             }
             // (random weights: a gate_up whose columns were packed in down's row order is just another random matrix)
             L.down.perm_folded = L.down.perm && L.gate_up.qw;

@@ -1,6 +1,6 @@
 // GPTQ-INT4 dequant-GEMM for gfx950: what the INT4 kernel translation units share — w4_skinny.hip (16-row supertile kernel
 // and the in-launch routing prologues), w4_moe_em.hip (expert-major grouped GEMMs), w4_decode.hip (dense decode kernels
-// and the dense dispatcher), w4_tiles.hip (64- to 256-row tiles).  Private to them: runner.hip and abi.cc see kernels.h.
+// and the dense dispatcher), w4_tiles.hip (64- to 256-row tiles).  Private to them: the runner (runner_*.hip) and the C-ABI layer (abi.cc, abi_gptq.cc) see kernels.h.
 //
 // Replaces, on the reference side: `GptqLinear::forward` → `B::load_gptq` + Marlin
 // (ferrum-quantization/src/gptq.rs:42-112, ferrum-kernels/src/backend/cuda/marlin.rs:488-633)
@@ -26,6 +26,7 @@
 #include "kernels.h"
 #include "knobs.h"
 #include "w4_device.h"
+#include "w4_upload.h"
 
 namespace fh {
 
@@ -99,8 +100,8 @@ typedef uint32_t u32x4 __attribute__((ext_vector_type(4)));
 // ───────────────────── launcher facts, each derived once (host) ─────────────────────
 
 // distance between the experts of a stack: dwords of qw, halves of sc (and of zp)
-inline long expert_stride_qw(const W4Device& w) { return (long)w.n64 * w.G * 4 * 64 * 4; }
-inline long expert_stride_sc(const W4Device& w) { return (long)w.n64 * w.G * 16 * 4; }
+inline long expert_stride_qw(const W4Device& w) { return (long)w4_qw_words(w.n64, w.G); }
+inline long expert_stride_sc(const W4Device& w) { return (long)w4_sc_elems(w.n64, w.G); }
 
 // 16-row tiles per wave of the skinny kernels
 inline int skinny_row_tiles(int m) { return m <= 16 ? 1 : (m <= 32 ? 2 : 4); }

@@ -3,7 +3,7 @@
 #include <vector>
 
 #include "common.h"
-#include "kernels.h"
+#include "w4_upload.h"
 
 namespace fh {
 
@@ -28,6 +28,15 @@ static inline uint16_t f32_to_f16_bits(float f) {
     uint16_t u;
     memcpy(&u, &h, 2);
     return u;
+}
+
+// fused gate_up column order: supertile st = [gate 32st.. | up I+32st..]
+std::vector<int32_t> gate_up_col_perm(int n) {
+    std::vector<int32_t> p(n);
+    const int I = n / 2;
+    for (int st = 0; st < n / 64; st++)
+        for (int c = 0; c < 64; c++) p[st * 64 + c] = c < 32 ? st * 32 + c : I + st * 32 + (c - 32);
+    return p;
 }
 
 int w4_repack_host(const int32_t* qweight, const float* scales, const int32_t* qzeros,
@@ -69,9 +78,9 @@ int w4_repack_host(const int32_t* qweight, const float* scales, const int32_t* q
         if ((uint32_t)qzeros[i] != 0x77777777u) { symmetric = false; break; }
 
     out->k = k; out->n = n; out->n64 = n64; out->G = G; out->symmetric = symmetric;
-    out->qw.assign((size_t)n64 * G * 4 * 64 * 4, 0);
-    out->sc.assign((size_t)n64 * G * 16 * 4, 0);
-    if (!symmetric) out->zp.assign((size_t)n64 * G * 16 * 4, f32_to_f16_bits(8.0f));
+    out->qw.assign(w4_qw_words(n64, G), 0);
+    out->sc.assign(w4_sc_elems(n64, G), 0);
+    if (!symmetric) out->zp.assign(w4_sc_elems(n64, G), f32_to_f16_bits(8.0f));
     else out->zp.clear();
     out->perm = perm;
 

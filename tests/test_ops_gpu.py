@@ -1039,6 +1039,54 @@ def test_moe_asymmetric_and_act_order_expert_stacks(env, tokens, E, K, H, I, asy
     assert torch.equal(xd, x_keep)                                         # the gather works on a scratch copy
 
 
+def mixed_stack_case(O, asym_experts, tokens=5, E=3, K=2, H=256, I=128):
+    """Inputs and the dequantised CPU reference of test_moe_mixed_symmetric_and_asymmetric_expert_stack (no GPU involved)."""
+    rng = np.random.default_rng(1000 + 7 * sum(1 << e for e in asym_experts))
+    gu = [O.make_synthetic_gptq(H, 2 * I, 128, 700 + e, symmetric=e not in asym_experts) for e in range(E)]
+    dn = [O.make_synthetic_gptq(I, H, 128, 900 + e, symmetric=e not in asym_experts) for e in range(E)]
+    gu = [(q, f16r(s / (0.28 * np.sqrt(H))), z) for q, s, z in gu]
+    dn = [(q, f16r(s / (0.28 * np.sqrt(I))), z) for q, s, z in dn]
+    x = f16r(rng.standard_normal((tokens, H)))
+    rid, rw = O.route_topk(rng.standard_normal((tokens, E)).astype(np.float32), E, K, True)
+    gw = np.stack([O.dequant_gptq(q, s, z, 128, H, 2 * I) for q, s, z in gu])
+    dw = np.stack([O.dequant_gptq(q, s, z, 128, I, H) for q, s, z in dn])
+    return gu, dn, x, rid, rw, O.moe_forward_cpu(x, H, I, K, rid, rw, gw, dw)
+
+
+@pytest.mark.parametrize("asym_experts", [(1,), (0,)], ids=["sym-asym-sym", "asym-sym-sym"])
+def test_moe_mixed_symmetric_and_asymmetric_expert_stack(env, asym_experts, forms):
+    """A stack that mixes symmetric and asymmetric experts: the zero-point array arrives with the first asymmetric expert,
+    after (sym, asym, sym) or before (asym, sym, sym) symmetric experts have been written, and those carry the explicit zero
+    point 8.0.  Two quant groups, fused gate_up, 16-row blocks; bound of test_moe_asymmetric_and_act_order_expert_stacks."""
+    pkg, B, ctx, O, torch = env
+    tokens, E, K, H, I = 5, 3, 2, 256, 128
+    gu, dn, x, rid, rw, ref = mixed_stack_case(O, asym_experts)
+    assert np.isfinite(ref).all() and set(rid.reshape(-1).tolist()) == set(range(E))      # every expert holds a pair
+    P = tokens * K
+    ids_d = torch.from_numpy(rid.astype(np.int32).reshape(-1).copy()).cuda()
+    xd, wd = dev16(torch, x), torch.from_numpy(rw.reshape(-1).copy()).cuda()
+    stack = B.load_gptq_stacked([q for q, _, _ in gu], [s for _, s, _ in gu], [z for _, _, z in gu], None, 4, 128, H, 2 * I,
+                                fuse_gate_up=True)
+    down_stack = B.load_gptq_stacked([q for q, _, _ in dn], [s for _, s, _ in dn], [z for _, _, z in dn], None, 4, 128, I, H)
+    sd = torch.empty(P + E * 16, dtype=torch.int32, device="cuda")
+    bd = torch.empty((P + E * 16) // 16 + 1, dtype=torch.int32, device="cuda")
+    td = torch.zeros(1, dtype=torch.int32, device="cuda")
+    B.moe_align_block_size_pair_ids(ctx, ids_d, sd, bd, td, P, E, 16, P + E * 16)
+    mb = (P + E * 16) // 16
+    act = torch.full((P, I), float("nan"), dtype=torch.float16, device="cuda")
+    down = torch.full((P, H), float("nan"), dtype=torch.float16, device="cuda")
+    forms.reset()
+    stack.gemm_phase_vllm(ctx, xd, sd, bd, td, act, P, 16, K, mb, fused_silu_mul=True)
+    down_stack.gemm_phase_vllm(ctx, act, sd, bd, td, down, P, 16, 1, mb)
+    forms.require("moe_block16")
+    out = torch.zeros(tokens, H, dtype=torch.float16, device="cuda")
+    B.moe_combine(ctx, down, wd, out, tokens, K, H)
+    ctx.sync()
+    err = nmse(ref, host(out))
+    print("mixed stack", asym_experts, "nmse", err)
+    assert err < 3e-6
+
+
 @pytest.mark.parametrize("tokens,H,E,K", [(1, 2048, 128, 8), (32, 2048, 128, 8), (5, 1024, 64, 4), (3, 4096, 16, 2)])
 def test_fused_add_rms_norm_route_equals_op_chain(env, tokens, H, E, K):
     # fused.hip B ≡ fused_add_rms_norm → gemm(router) → route_topk_softmax, each as the oracle defines it
