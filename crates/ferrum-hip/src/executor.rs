@@ -224,7 +224,69 @@ impl DecoderOnlyLLM for HipDecoderModel {
     }
 }
 
+/// How `embed_tokens` pools the residual stream (`FerrumHipEmbedOptions`).
+#[derive(Clone, Copy, Debug, PartialEq, Eq)]
+pub enum EmbedPooling {
+    LastToken,
+    Mean,
+    FirstToken,
+}
+#[derive(Clone, Copy, Debug)]
+pub struct EmbedOptions {
+    pub pooling: EmbedPooling,
+    pub normalize: bool,
+    /// 0 = the hidden size; else the leading components kept (cut first, normalised after)
+    pub dims: usize,
+    pub final_norm: bool,
+}
+impl Default for EmbedOptions {
+    fn default() -> Self {
+        EmbedOptions { pooling: EmbedPooling::LastToken, normalize: true, dims: 0, final_norm: true }
+    }
+}
+
+/// Sequence ids of `embed_tokens`: a range the cache-id map (counting up from 1) never reaches; each call releases its own.
+const EMBED_SEQ_BASE: u64 = 1 << 63;
+
 impl HipDecoderModel {
+    /// Width of an embedding with `dims == 0`.
+    pub fn embedding_dim(&self) -> usize {
+        let mut h = 0 as c_int;
+        unsafe { ffi::ferrum_hip_model_embedding_dim(self.m, &mut h) };
+        h as usize
+    }
+
+    /// One embedding per token sequence: the prefill forward with the sampling head replaced by final norm → pool → cut → L2
+    /// (`ferrum_hip_model_embed`), each sequence whole in the call and released before it returns — what an `EmbedModel`
+    /// adapter calls.  The batch must fit the runner's max_seqs / max_tokens; the caller splits larger requests.
+    pub fn embed_tokens(&self, seqs: &[&[u32]], opts: EmbedOptions) -> Result<Vec<Vec<f32>>> {
+        if seqs.is_empty() {
+            return Ok(Vec::new());
+        }
+        let hidden = self.embedding_dim();
+        if opts.dims > hidden {
+            return Err(FerrumError::model(format!("embed_tokens: dims {} > hidden {}", opts.dims, hidden)));
+        }
+        let d = if opts.dims == 0 { hidden } else { opts.dims };
+        let c_items: Vec<ffi::FerrumHipBatchItem> = seqs.iter().enumerate().map(|(j, toks)| ffi::FerrumHipBatchItem {
+            seq_id: EMBED_SEQ_BASE + j as u64, q_tokens: toks.as_ptr(), num_q_tokens: toks.len() as i32, pos_offset: 0, is_final_chunk: 1, _pad: 0,
+        }).collect();
+        let c_opts = ffi::FerrumHipEmbedOptions {
+            pooling: match opts.pooling { EmbedPooling::LastToken => 0, EmbedPooling::Mean => 1, EmbedPooling::FirstToken => 2 },
+            normalize: opts.normalize as i32, dims: opts.dims as i32, skip_final_norm: !opts.final_norm as i32, release: 1, _pad: 0,
+        };
+        let mut out = vec![0f32; seqs.len() * d];
+        let rc = unsafe { ffi::ferrum_hip_model_embed(self.m, c_items.as_ptr(), c_items.len() as c_int, &c_opts, out.as_mut_ptr()) };
+        if rc != ffi::FERRUM_HIP_OK {
+            // (a forward that failed behind the admission has not released: nothing of this call may stay reserved)
+            for it in &c_items {
+                unsafe { ffi::ferrum_hip_model_release(self.m, it.seq_id) };
+            }
+        }
+        check(rc)?;
+        Ok(out.chunks(d).map(|v| v.to_vec()).collect())
+    }
+
     fn blocks_of(&self, id: u64) -> usize {
         let (mut nb, mut kv) = (0 as c_int, 0 as c_int);
         // (unknown sequence → 0 blocks; the entry point reports the count without copying when capacity is 0)

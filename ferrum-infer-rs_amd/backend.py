@@ -249,6 +249,16 @@ class HipBackend:
                "embedding_lookup")
 
     @staticmethod
+    def embed_pool(ctx, hidden, seq_rows, norm_w, eps, pooling, normalize, dims, out, num_seqs, dim):
+        """The embedding tail (csrc/embed_pool.hip): per span {begin, end} of seq_rows [num_seqs, 2] int32, final norm (norm_w None:
+        none) → pool (0 last, 1 mean, 2 first) → cut to dims (0 = dim) → L2, fp32 out [num_seqs, dims or dim].  hidden [rows, dim]
+        fp16 or fp32."""
+        import torch
+        fn = ctx.lib.ferrum_hip_embed_pool_f32 if hidden.dtype == torch.float32 else ctx.lib.ferrum_hip_embed_pool_f16
+        _check(fn(_ptr(hidden), _ptr(seq_rows), _ptr(norm_w), C.c_float(eps), int(pooling), int(normalize), int(dims), _ptr(out),
+                  int(num_seqs), int(dim), ctx.ws, ctx.stream), "embed_pool")
+
+    @staticmethod
     def layer_norm(ctx, x, gamma, beta, eps, out, tokens, dim):
         _check(ctx.lib.ferrum_hip_layer_norm_f16(_ptr(x), _ptr(gamma), _ptr(beta), C.c_float(eps), _ptr(out), tokens, dim, ctx.stream), "layer_norm")
 

@@ -179,6 +179,22 @@ int ferrum_hip_gather_columns_f16(const void* in, const int32_t* perm, void* out
     return gather_columns_f16(CH(in), perm, H(out), rows, cols, ST(stream));
 }
 
+// ── the embedding tail (embed_pool.hip), exported for the element-wise tests ──
+static int embed_pool_export(const void* hidden, bool f32, const int32_t* seq_rows, const void* norm_w, float eps, int pooling, int normalize,
+                             int dims, float* out, int num_seqs, int dim, FerrumHipWorkspace* ws, void* stream) {
+    FH_REQUIRE(num_seqs <= 0 || (hidden && seq_rows && out), "embed_pool: null buffer");
+    return embed_pool(hidden, f32, seq_rows, CH(norm_w), eps, pooling, normalize, dims, out, num_seqs, dim, 0, ws ? ws->ptr : nullptr,
+                      ws ? ws->bytes : 0, ST(stream));
+}
+int ferrum_hip_embed_pool_f16(const void* hidden, const int32_t* seq_rows, const void* norm_w, float eps, int pooling, int normalize,
+                              int dims, float* out, int num_seqs, int dim, FerrumHipWorkspace* ws, void* stream) {
+    return embed_pool_export(hidden, false, seq_rows, norm_w, eps, pooling, normalize, dims, out, num_seqs, dim, ws, stream);
+}
+int ferrum_hip_embed_pool_f32(const float* hidden, const int32_t* seq_rows, const void* norm_w, float eps, int pooling, int normalize,
+                              int dims, float* out, int num_seqs, int dim, FerrumHipWorkspace* ws, void* stream) {
+    return embed_pool_export(hidden, true, seq_rows, norm_w, eps, pooling, normalize, dims, out, num_seqs, dim, ws, stream);
+}
+
 int ferrum_hip_layer_norm_f16(const void* x, const void* gamma, const void* beta, float eps, void* out, int tokens, int dim, void* stream) {
     FH_REQUIRE(tokens == 0 || (x && gamma && beta && out), "layer_norm: null buffer");
     return layer_norm_f16(CH(x), CH(gamma), CH(beta), eps, H(out), tokens, dim, ST(stream));

@@ -132,6 +132,14 @@ int fused_gated_act_slabs_f16(const float* slabs, int S, long slab_stride, int l
                               hipStream_t s);
 int rms_norm_f32_to_f16(const float* x, const int32_t* row_idx, const __half* w, float eps, __half* out, int n_rows, int dim,
                         hipStream_t s);
+// ── embedding tail (embed_pool.hip; launch plan: embed_plan.h) ───────────────
+// out[i][0 .. d) = L2(cut(pool over rows [seq_rows[2i], seq_rows[2i+1]) of rms_norm(hidden)·norm_w)), d = dims ? dims : dim, all fp32.
+// hidden [rows, dim] fp16 or fp32; norm_w NULL: no norm; pooling 0 last row, 1 mean, 2 first row; max_span_rows ≤ 0: unknown.
+// Mean pooling keeps fp32 partials [num_seqs][chunks][dim] (+ [num_seqs][groups][dim] for spans of more than 32 chunks) in the
+// workspace.  Bit-identical from run to run and whatever else the launch holds (no atomics, chunk seams from the span's own
+// length, fixed summation order).
+int embed_pool(const void* hidden, bool hidden_f32, const int32_t* seq_rows, const __half* norm_w, float eps, int pooling, int normalize,
+               int dims, float* out, int num_seqs, int dim, int max_span_rows, float* workspace, size_t workspace_bytes, hipStream_t s);
 // contiguous-KV lane (contig_ops.hip)
 int split_qkv_f16(const __half* qkv, __half* q, __half* k, __half* v, int tokens, int q_dim, int kv_dim, hipStream_t s);
 int qk_norm_rope_f16(const __half* input, const __half* norm_w, const float* cos_t, const float* sin_t, __half* output,

@@ -36,7 +36,7 @@ struct LayerWeights {
 
 // Layout of the per-forward index block (host pinned mirror → device).
 struct IndexLayout {
-    size_t tokens, cu_seqlens, pos_offsets, kv_lens, sampled_idx, block_tables, total;
+    size_t tokens, cu_seqlens, pos_offsets, kv_lens, sampled_idx, embed_spans, block_tables, total;
 };
 
 }  // namespace fh
@@ -119,6 +119,8 @@ struct FerrumHipModel {
     float* expert_w = nullptr;
     float* logits = nullptr;       // [max_seqs, V] fp32
     uint32_t* out_tokens = nullptr;   // [max_seqs]
+    float* embed_out = nullptr;       // [max_seqs, hidden] fp32: the vectors of ferrum_hip_model_embed (allocated by its first call)
+    size_t embed_out_bytes = 0;
     float* workspace = nullptr;
     size_t workspace_bytes = 0;
     float* taps = nullptr;         // [L, max_tokens, H] fp32 when enabled
@@ -189,10 +191,12 @@ struct StepShape {
 };
 
 // The index block (layout m->il) as typed pointers: over the pinned host copy the callers fill, or over the device copy the kernels read
-struct IndexBlock { uint32_t *tokens, *cu, *pos, *kvl; int32_t *sampled_idx, *bt; };
+// (embed_spans: the {begin, end} rows of every final-chunk item, what the embedding tail pools over)
+struct IndexBlock { uint32_t *tokens, *cu, *pos, *kvl; int32_t *sampled_idx, *bt, *embed_spans; };
 inline IndexBlock index_block(const FerrumHipModel* m, uint8_t* b) {
     return {(uint32_t*)(b + m->il.tokens), (uint32_t*)(b + m->il.cu_seqlens), (uint32_t*)(b + m->il.pos_offsets),
-            (uint32_t*)(b + m->il.kv_lens), (int32_t*)(b + m->il.sampled_idx), (int32_t*)(b + m->il.block_tables)};
+            (uint32_t*)(b + m->il.kv_lens), (int32_t*)(b + m->il.sampled_idx), (int32_t*)(b + m->il.block_tables),
+            (int32_t*)(b + m->il.embed_spans)};
 }
 
 struct GreedyDeviceOpts {          // device pointers, already uploaded on m->stream
@@ -200,9 +204,13 @@ struct GreedyDeviceOpts {          // device pointers, already uploaded on m->st
     const uint32_t* row_offsets = nullptr; const uint32_t* token_ids = nullptr; const float* penalties = nullptr;
 };
 
+// The embedding tail in place of the sampling head: pool the final-chunk items' spans (index block, embed_spans) of the residual
+// stream into out [num_sampled, dims ? dims : hidden] fp32 (embed_pool.hip)
+struct EmbedHead { int pooling, normalize, dims; bool final_norm; int max_span_rows; float* out; };
+
 // runner_forward.hip
 int enqueue_forward(FerrumHipModel* m, const StepShape& sh, bool greedy, const GreedyDeviceOpts* gopts = nullptr,
-                    const DecodeAdvance* advance = nullptr, int* advance_fused = nullptr);
+                    const DecodeAdvance* advance = nullptr, int* advance_fused = nullptr, const EmbedHead* embed = nullptr);
 const int32_t* moe_ids(const FerrumHipModel* m);
 int moe_max_blocks(int P, int E);
 bool moe_expert_major(const FerrumHipModel* m, int P);

@@ -694,15 +694,24 @@ struct ForwardPass {
         if (advance && advance_fused) *advance_fused = 1;
         return 0;
     }
+    // the embedding tail instead: final norm (fp32, never rounded) → pool over each final-chunk item's rows → cut → L2.  The
+    // residual stream is complete here in every form: behind the last layer no chain launch follows, so its tail has run.
+    int embed_head(const EmbedHead& eh) {
+        if (sh.num_sampled <= 0) return 0;
+        const void* rows = sandwich ? (const void*)m->residual_f32 : (const void*)m->residual;
+        return embed_pool(rows, sandwich, ix.embed_spans, eh.final_norm ? m->final_norm : nullptr, c.rms_eps, eh.pooling, eh.normalize, eh.dims,
+                          eh.out, sh.num_sampled, H, eh.max_span_rows, m->workspace, m->workspace_bytes, s);
+    }
 };
 #undef RUN
 
 }  // namespace
 
 // Enqueue one forward: head, the layers — each as one of the chain forms (decided per layer, the next layer's decision known, so
-// that a tail can be left to its launch) or as q|k|v + attention and the MLP block — then the sampling head.
+// that a tail can be left to its launch) or as q|k|v + attention and the MLP block — then the sampling head, or (`embed`) the
+// embedding tail in its place.
 int fh::enqueue_forward(FerrumHipModel* m, const StepShape& sh, bool greedy, const GreedyDeviceOpts* gopts, const DecodeAdvance* advance,
-                        int* advance_fused) {
+                        int* advance_fused, const EmbedHead* embed) {
     if (advance_fused) *advance_fused = 0;
     const int n_layers = m->cfg.num_layers;
     ForwardPass f(m, sh);
@@ -724,6 +733,7 @@ int fh::enqueue_forward(FerrumHipModel* m, const StepShape& sh, bool greedy, con
         plan = next;
     }
     m->taps_tokens = sh.m_total;
+    if (embed) return f.embed_head(*embed);
     return f.sample_head(greedy, gopts, advance, advance_fused);
 }
 #undef FH_TRY

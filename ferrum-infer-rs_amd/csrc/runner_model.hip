@@ -191,7 +191,7 @@ int ferrum_hip_model_destroy(FerrumHipModel* m) {
                     (void*)m->route_cand, (void*)m->route_stats, (void*)m->route_arrive, (void*)m->cos_local,
                     (void*)m->sin_local, (void*)m->residual_f32, (void*)m->gather_scratch, (void*)m->greedy_opts_dev, (void*)m->tp_tmp,
                     (void*)m->expert_ids_local, (void*)m->ones, m->vp_pairs, m->vp_gathered,
-                    (void*)m->kv_pools_dev, (void*)m->kv_pairs_dev, (void*)m->kv_staging})
+                    (void*)m->kv_pools_dev, (void*)m->kv_pairs_dev, (void*)m->kv_staging, (void*)m->embed_out})
         if (p) (void)hipFree(p);
     if (m->idx_host) (void)hipHostFree(m->idx_host);
     if (m->inlaunch_timeouts) (void)hipHostFree(m->inlaunch_timeouts);
@@ -605,6 +605,7 @@ int ferrum_hip_model_finalize(FerrumHipModel* m) {
     m->il.pos_offsets = take(S * 4);
     m->il.kv_lens = take(S * 4);
     m->il.sampled_idx = take(S * 4);
+    m->il.embed_spans = take(S * 8);
     m->il.block_tables = take(S * m->max_blocks_per_seq * 4);
     m->il.total = off;
     FH_CHECK_HIP(hipHostMalloc((void**)&m->idx_host, off, hipHostMallocDefault));

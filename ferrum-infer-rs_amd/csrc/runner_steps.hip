@@ -1,4 +1,5 @@
 // Decoder runner, the drivers of the forward: ferrum_hip_model_unified_forward{,_ex} (admission, index block, one forward),
+// ferrum_hip_model_embed (the same forward with the embedding tail in place of the sampling head),
 // ferrum_hip_model_decode_steps (the steady-state decode loop: one step captured into a hipGraph and replayed) and the bench's
 // ferrum_hip_model_time_kernel.
 #include "runner.h"
@@ -62,20 +63,13 @@ static void fill_block_table_row(const FerrumHipModel* m, int32_t* row, const Se
     for (int b = 0; b < m->max_blocks_per_seq; b++) row[b] = b < (int)st.blocks.size() ? (int32_t)st.blocks[b] : 0;
 }
 
-extern "C" {
-
-int ferrum_hip_model_unified_forward(FerrumHipModel* m, const FerrumHipBatchItem* items, int num_items, int greedy,
-                                     uint32_t* out_tokens, float* logits_out) {
-    return ferrum_hip_model_unified_forward_ex(m, items, num_items, greedy, nullptr, out_tokens, logits_out);
-}
-
-int ferrum_hip_model_unified_forward_ex(FerrumHipModel* m, const FerrumHipBatchItem* items, int num_items, int greedy,
-                                        const FerrumHipGreedyOptions* opts, uint32_t* out_tokens, float* logits_out) {
-    FH_REQUIRE(m && m->finalized, "unified_forward: model not finalized");
-    if (num_items <= 0) return 0;
-    FH_REQUIRE(items, "unified_forward: null items");
+// The front of a forward over batch items (ferrum_hip_model_unified_forward_ex, ferrum_hip_model_embed): argument checks, the
+// step's shape, KV admission, the index block (tokens, cu_seqlens, positions, kv lengths, sampled rows, the final-chunk items'
+// row spans, block tables) filled and sent.  `who` names the entry point in the messages.
+static int admit_and_upload(FerrumHipModel* m, const FerrumHipBatchItem* items, int num_items, const char* who, StepShape* shape) {
+    FH_REQUIRE(items, "%s: null items", who);
     const FerrumHipModelConfig& c = m->cfg;
-    FH_REQUIRE(num_items <= c.max_seqs, "unified_forward: %d items > max_seqs %d", num_items, c.max_seqs);
+    FH_REQUIRE(num_items <= c.max_seqs, "%s: %d items > max_seqs %d", who, num_items, c.max_seqs);
     // shape + admission
     StepShape sh{};
     sh.num_seqs = num_items;
@@ -83,12 +77,12 @@ int ferrum_hip_model_unified_forward_ex(FerrumHipModel* m, const FerrumHipBatchI
     std::vector<FerrumHipKvSlotRequest> reqs(num_items);
     for (int i = 0; i < num_items; i++) {
         const FerrumHipBatchItem& it = items[i];
-        FH_REQUIRE(it.num_q_tokens > 0 && it.q_tokens, "unified_forward: item %d has no tokens", i);
+        FH_REQUIRE(it.num_q_tokens > 0 && it.q_tokens, "%s: item %d has no tokens", who, i);
         const int have = m->seqs->len(it.seq_id);
-        FH_REQUIRE(it.pos_offset == have, "unified_forward: item %d pos_offset=%d but cache holds %d tokens", i, it.pos_offset, have);
-        FH_REQUIRE(it.pos_offset + it.num_q_tokens <= c.max_seq_len, "unified_forward: item %d exceeds max_seq_len %d", i, c.max_seq_len);
+        FH_REQUIRE(it.pos_offset == have, "%s: item %d pos_offset=%d but cache holds %d tokens", who, i, it.pos_offset, have);
+        FH_REQUIRE(it.pos_offset + it.num_q_tokens <= c.max_seq_len, "%s: item %d exceeds max_seq_len %d", who, i, c.max_seq_len);
         for (int t = 0; t < it.num_q_tokens; t++)
-            FH_REQUIRE(it.q_tokens[t] < (uint32_t)c.vocab, "unified_forward: item %d token %u out of vocab", i, it.q_tokens[t]);
+            FH_REQUIRE(it.q_tokens[t] < (uint32_t)c.vocab, "%s: item %d token %u out of vocab", who, i, it.q_tokens[t]);
         sh.m_total += it.num_q_tokens;
         sh.max_q_len = std::max(sh.max_q_len, it.num_q_tokens);
         sh.max_kv_len = std::max(sh.max_kv_len, it.pos_offset + it.num_q_tokens);
@@ -96,7 +90,7 @@ int ferrum_hip_model_unified_forward_ex(FerrumHipModel* m, const FerrumHipBatchI
         if (it.is_final_chunk) sh.num_sampled++;
         reqs[i] = {it.seq_id, it.pos_offset + it.num_q_tokens, 0};
     }
-    FH_REQUIRE(sh.m_total <= c.max_tokens, "unified_forward: %d tokens > max_tokens %d", sh.m_total, c.max_tokens);
+    FH_REQUIRE(sh.m_total <= c.max_tokens, "%s: %d tokens > max_tokens %d", who, sh.m_total, c.max_tokens);
     sh.all_single_token = sh.pure_decode;
     if (c.sliding_window > 0 && c.sliding_window_pattern == 0) sh.pure_decode = false;   // uniform window: no full-attention layer
     if (int rc = m->seqs->reserve(reqs.data(), num_items, nullptr)) return rc;
@@ -111,7 +105,11 @@ int ferrum_hip_model_unified_forward_ex(FerrumHipModel* m, const FerrumHipBatchI
         t += it.num_q_tokens;
         h.pos[i] = (uint32_t)it.pos_offset;
         h.kvl[i] = (uint32_t)(it.pos_offset + it.num_q_tokens);
-        if (it.is_final_chunk) h.sampled_idx[j++] = t - 1;
+        if (it.is_final_chunk) {
+            h.embed_spans[2 * j] = t - it.num_q_tokens;
+            h.embed_spans[2 * j + 1] = t;
+            h.sampled_idx[j++] = t - 1;
+        }
         fill_block_table_row(m, h.bt + (size_t)i * m->max_blocks_per_seq, *m->seqs->find(it.seq_id));
     }
     h.cu[num_items] = (uint32_t)t;
@@ -123,6 +121,23 @@ int ferrum_hip_model_unified_forward_ex(FerrumHipModel* m, const FerrumHipBatchI
     // only the used prefix of the block-table region needs to travel
     size_t used = m->il.block_tables + (size_t)num_items * m->max_blocks_per_seq * 4;
     FH_CHECK_HIP(hipMemcpyAsync(m->idx_dev, m->idx_host, used, hipMemcpyHostToDevice, m->stream));
+    *shape = sh;
+    return 0;
+}
+
+extern "C" {
+
+int ferrum_hip_model_unified_forward(FerrumHipModel* m, const FerrumHipBatchItem* items, int num_items, int greedy,
+                                     uint32_t* out_tokens, float* logits_out) {
+    return ferrum_hip_model_unified_forward_ex(m, items, num_items, greedy, nullptr, out_tokens, logits_out);
+}
+
+int ferrum_hip_model_unified_forward_ex(FerrumHipModel* m, const FerrumHipBatchItem* items, int num_items, int greedy,
+                                        const FerrumHipGreedyOptions* opts, uint32_t* out_tokens, float* logits_out) {
+    FH_REQUIRE(m && m->finalized, "unified_forward: model not finalized");
+    if (num_items <= 0) return 0;
+    StepShape sh{};
+    if (int rc = admit_and_upload(m, items, num_items, "unified_forward", &sh)) return rc;
     GreedyDeviceOpts g{};
     if (greedy && opts && sh.num_sampled > 0) {
         // device copies of the greedy options live in a growable side buffer: [mask | row_offsets | token_ids | penalties]
@@ -165,6 +180,49 @@ int ferrum_hip_model_unified_forward_ex(FerrumHipModel* m, const FerrumHipBatchI
     FH_CHECK_HIP(hipStreamSynchronize(m->stream));
     for (int i = 0; i < num_items; i++) m->seqs->advance(items[i].seq_id, items[i].num_q_tokens);
     return check_inlaunch_waits(m);
+}
+
+int ferrum_hip_model_embedding_dim(const FerrumHipModel* m, int* hidden) {
+    FH_REQUIRE(m && hidden, "model_embedding_dim: null");
+    *hidden = m->cfg.hidden;
+    return 0;
+}
+
+int ferrum_hip_model_embed(FerrumHipModel* m, const FerrumHipBatchItem* items, int num_items, const FerrumHipEmbedOptions* opts,
+                           float* out_host) {
+    FH_REQUIRE(m && m->finalized, "model_embed: model not finalized");
+    const FerrumHipModelConfig& c = m->cfg;
+    const FerrumHipEmbedOptions o = opts ? *opts : FerrumHipEmbedOptions{0, 1, 0, 0, 0, 0};
+    // pre-flight: nothing is reserved or launched for a request that cannot be served
+    FH_REQUIRE(o.pooling >= 0 && o.pooling <= 2, "model_embed: pooling=%d must be 0 (last), 1 (mean) or 2 (first)", o.pooling);
+    FH_REQUIRE(o.dims >= 0 && o.dims <= c.hidden, "model_embed: dims=%d must be 0 (all) or in [1, hidden=%d]", o.dims, c.hidden);
+    if (num_items <= 0) return 0;
+    FH_REQUIRE(items, "model_embed: null items");
+    int num_final = 0;
+    for (int i = 0; i < num_items; i++) {
+        if (!items[i].is_final_chunk) continue;
+        num_final++;
+        FH_REQUIRE(o.pooling == 0 || items[i].pos_offset == 0,
+                   "model_embed: item %d (sequence %llu) ends its sequence at pos_offset=%d: %s pooling needs the whole sequence in this "
+                   "forward (only last-token pooling works over chunks or a cached prefix)",
+                   i, (unsigned long long)items[i].seq_id, items[i].pos_offset, o.pooling == 1 ? "mean" : "first-token");
+    }
+    FH_REQUIRE(num_final == 0 || out_host, "model_embed: null output");
+    if (int rc = grow_device((void**)&m->embed_out, &m->embed_out_bytes, (size_t)c.max_seqs * c.hidden * sizeof(float), m->stream)) return rc;
+    StepShape sh{};
+    if (int rc = admit_and_upload(m, items, num_items, "model_embed", &sh)) return rc;
+    const int d = o.dims ? o.dims : c.hidden;
+    const EmbedHead eh{o.pooling, o.normalize != 0, o.dims, o.skip_final_norm == 0, sh.max_q_len, m->embed_out};
+    if (int rc = enqueue_forward(m, sh, false, nullptr, nullptr, nullptr, &eh)) return rc;
+    if (num_final > 0)
+        FH_CHECK_HIP(hipMemcpyAsync(out_host, m->embed_out, (size_t)num_final * d * sizeof(float), hipMemcpyDeviceToHost, m->stream));
+    FH_CHECK_HIP(hipStreamSynchronize(m->stream));
+    for (int i = 0; i < num_items; i++) m->seqs->advance(items[i].seq_id, items[i].num_q_tokens);
+    const int rc = check_inlaunch_waits(m);
+    if (o.release)
+        for (int i = 0; i < num_items; i++)
+            if (items[i].is_final_chunk) (void)ferrum_hip_model_release(m, items[i].seq_id);
+    return rc;
 }
 
 int ferrum_hip_model_decode_steps(FerrumHipModel* m, const uint64_t* seq_ids, const uint32_t* first_tokens, int n,

@@ -37,6 +37,15 @@ class GreedyOptions(C.Structure):
                 ("penalties", C.POINTER(C.c_float))]
 
 
+class EmbedOptions(C.Structure):
+    """FerrumHipEmbedOptions: how ferrum_hip_model_embed pools the residual stream."""
+    _fields_ = [("pooling", C.c_int32), ("normalize", C.c_int32), ("dims", C.c_int32), ("skip_final_norm", C.c_int32),
+                ("release", C.c_int32), ("_pad", C.c_int32)]
+
+
+POOLING = {"last": 0, "mean": 1, "first": 2}
+
+
 class KvSlotRequest(C.Structure):
     _fields_ = [("seq_id", C.c_uint64), ("target_len", C.c_int32), ("_pad", C.c_int32)]
 
@@ -403,6 +412,29 @@ class HipModel:
             toks.ctypes.data_as(C.POINTER(C.c_uint32)),
             None if logits is None else logits.ctypes.data_as(C.POINTER(C.c_float))), "unified_forward")
         return (toks[:n_final] if greedy else None), (logits[:n_final] if logits is not None else None)
+
+    def embed(self, items, pooling="last", normalize=True, dims=0, final_norm=True, release=False):
+        """items as for unified_forward.  The forward with the sampling head replaced by final norm → pool → cut → L2
+        (ferrum_hip_model_embed): fp32 [n_final, dims or hidden], one row per final-chunk item in item order.  pooling "last" works
+        over chunks and behind a prefix-cache hit; "mean" / "first" need the whole sequence in this call.  release: every embedded
+        sequence is released before the call returns."""
+        keep = [np.ascontiguousarray(t, dtype=np.uint32) for _, t, _, _ in items]
+        arr = (BatchItem * max(len(items), 1))()
+        n_final = 0
+        for i, (sid, _, pos, fin) in enumerate(items):
+            arr[i] = BatchItem(sid, keep[i].ctypes.data_as(C.POINTER(C.c_uint32)), len(keep[i]), pos, int(fin), 0)
+            n_final += int(bool(fin))
+        opts = EmbedOptions(POOLING[pooling] if isinstance(pooling, str) else int(pooling), int(bool(normalize)), int(dims),
+                            int(not final_norm), int(bool(release)), 0)
+        d = int(dims) if 0 < int(dims) <= self.cfg.hidden else self.cfg.hidden
+        out = np.zeros((max(n_final, 1), d), np.float32)
+        _check(self.lib.ferrum_hip_model_embed(self.h, arr, len(items), C.byref(opts), out.ctypes.data_as(C.POINTER(C.c_float))), "embed")
+        return out[:n_final]
+
+    def embedding_dim(self):
+        h = C.c_int()
+        _check(self.lib.ferrum_hip_model_embedding_dim(self.h, C.byref(h)), "embedding_dim")
+        return h.value
 
     def local_vocab(self):
         """(first vocabulary row, row count) this model scores: the whole vocabulary unless cfg.vocab_parallel."""

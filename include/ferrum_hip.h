@@ -105,6 +105,22 @@ int ferrum_hip_gather_rms_norm_f16(const void* x, const int32_t* row_idx, const 
 int ferrum_hip_fused_gated_act_slabs_f16(const float* slabs, int num_slabs, size_t slab_stride, int ld, void* out, int tokens,
                                          int intermediate, int gelu, void* stream);
 int ferrum_hip_gather_columns_f16(const void* in, const int32_t* perm, void* out, int rows, int cols, void* stream);
+/* The tail of an embedding forward (csrc/embed_pool.hip), device pointers: for span i of num_seqs, rows [seq_rows[2i],
+ * seq_rows[2i+1]) of hidden [rows, dim] (fp16, or fp32 for the `_f32` form):
+ *   1. norm each row in fp32, n_t = x_t · rsqrt(mean(x_t²) + eps) · norm_w — never rounded to fp16; norm_w NULL: n_t = x_t;
+ *   2. pool: pooling 0 = the span's last row, 1 = the mean of n_t over the span, 2 = its first row (0 / 2 read that row only);
+ *   3. cut: keep components [0, d), d = dims ? dims : dim (the Matryoshka cut: cut first, normalise after);
+ *   4. normalize != 0: out = v / max(‖v‖₂, 1e-12) — an all-zero vector gives exact zeros.
+ * out [num_seqs, d] fp32.  dim % 8 == 0, ≤ 16384; 0 ≤ dims ≤ dim; num_seqs ≤ 65535.  Mean pooling cuts a span into chunks of 16
+ * rows (doubled while the workspace cannot hold a span's partials), one workgroup each, fp32 partials [span][chunk][dim] in the
+ * workspace; a span of more than 32 chunks has them summed in groups of 16 by a launch of its own; the last launch adds a
+ * span's partials (or groups) in index order.  It needs a workspace of at least num_seqs · dim · 4 bytes, and takes up to 544
+ * times that.  No atomics, a span's chunk seams depend on its own length only and every sum has a fixed order: a span's vector
+ * is bit-identical from run to run and whatever else the launch holds. */
+int ferrum_hip_embed_pool_f16(const void* hidden, const int32_t* seq_rows, const void* norm_w, float eps, int pooling, int normalize,
+                              int dims, float* out, int num_seqs, int dim, FerrumHipWorkspace* ws, void* stream);
+int ferrum_hip_embed_pool_f32(const float* hidden, const int32_t* seq_rows, const void* norm_w, float eps, int pooling, int normalize,
+                              int dims, float* out, int num_seqs, int dim, FerrumHipWorkspace* ws, void* stream);
 /* Backend::layer_norm / Backend::gelu (traits.rs, required core ops; CPU cpu.rs:2081-2122 — exact-form GELU with the
  * reference's own erf polynomial, cpu.rs:2263-2273).  Not on the LLM decode path; present so that the binding returns
  * "unsupported" for no required method. */
@@ -660,6 +676,29 @@ typedef struct {
 int ferrum_hip_model_local_vocab(const FerrumHipModel* model, int* vocab_start, int* vocab_count);
 int ferrum_hip_model_unified_forward_ex(FerrumHipModel* model, const FerrumHipBatchItem* items, int num_items, int greedy,
                                         const FerrumHipGreedyOptions* opts, uint32_t* out_tokens, float* logits_out);
+/* Embeddings (ferrum-engine/src/embedding_engine.rs, `ferrum embed`, /v1/embeddings): the forward of
+ * ferrum_hip_model_unified_forward with the sampling head replaced — for every item with is_final_chunk, in item order,
+ * out_host[j·d ..] = the sequence's embedding, d = dims ? dims : hidden, fp32.  No lm_head GEMM, no logits: the model's final
+ * norm (fp32, not rounded to fp16) on the pooled rows of the residual stream, pool, cut, L2 (ferrum_hip_embed_pool_* above, with
+ * its determinism rule).  Non-final chunks only fill the KV cache.  Last-token pooling works with any chunking and behind a
+ * prefix-cache hit; mean and first-token pooling need the whole sequence in this forward: a final-chunk item with
+ * pos_offset != 0 is FERRUM_HIP_INVALID (the message names the item), returned — like pooling ∉ {0, 1, 2}, dims < 0 and
+ * dims > hidden — before anything is reserved or launched.  opts NULL: last token, normalised, all dims, with the final norm.
+ * release != 0: behind the copy-back every final-chunk sequence is released as by ferrum_hip_model_release, so the usual
+ * embedding request needs no second call; release == 0 leaves sequences that decode_steps / a further forward can continue.
+ * Tensor parallel: the residual stream is replicated behind the last all-reduce, so the call is rank-local — issue it on every
+ * rank, every rank returns the same vectors, nothing goes through the communicator. */
+typedef struct {
+    int32_t pooling;          /* 0 last token, 1 mean over the sequence, 2 first token */
+    int32_t normalize;        /* != 0: L2-normalise (after the cut) */
+    int32_t dims;             /* 0 = hidden; else 1..hidden leading components */
+    int32_t skip_final_norm;  /* 0 = the model's final norm on every pooled row */
+    int32_t release;          /* != 0: release each embedded sequence before returning */
+    int32_t _pad;
+} FerrumHipEmbedOptions;
+int ferrum_hip_model_embed(FerrumHipModel* model, const FerrumHipBatchItem* items, int num_items,
+                           const FerrumHipEmbedOptions* opts, float* out_host);
+int ferrum_hip_model_embedding_dim(const FerrumHipModel* model, int* hidden);
 /* Steady-state decode: every listed sequence advances by one token (its last sampled token),
  * `steps` times, with device-side greedy sampling and hipGraph replay when available.
  * out_tokens [steps, n] (may be NULL). */
