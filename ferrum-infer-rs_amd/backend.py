@@ -571,6 +571,80 @@ class HipBackend:
             hidden, ctx.stream), "moe_combine_add_rms_norm")
 
 
+_CHAIN_INTS = ("T", "H", "nq", "nkv", "head_dim", "has_a", "top_k", "a_S", "a_ld", "qk_mode", "max_blocks", "sliding_window", "E",
+               "r_top_k", "Q", "norm_topk", "defer_merge", "attn_splits")
+CHAIN_BUFFERS = ("down", "comb_w", "res_in", "ln_in", "a_slabs", "a_x", "res_a", "norm1", "qkv_out", "k_pool", "v_pool", "block_tables",
+                 "kv_lens", "q_norm_w", "k_norm_w", "cos_t", "sin_t", "attn_out", "o_part", "res_b_out", "post_ln", "norm2", "router_w",
+                 "cand", "stats", "ids", "weights", "attn_partial", "attn_tickets", "cnt", "cnt_next", "timeout")
+
+
+def _chain_fields():
+    """FerrumHipDecodeChainDesc, field for field in the header's order (tests/test_abi_symbols.py holds the order to the header)."""
+    order = ["T", "H", "nq", "nkv", "head_dim", "has_a", "top_k", "down", "comb_w", "res_in", "ln_in", "a_slabs", "a_S", "a_ld",
+             "a_slab_stride", "a_x", "eps", "res_a", "norm1", "qkv", "qkv_out", "k_pool", "v_pool", "block_tables", "kv_lens", "q_norm_w",
+             "k_norm_w", "cos_t", "sin_t", "qk_mode", "max_blocks", "sliding_window", "attn_out", "o", "o_part", "res_b_out", "post_ln",
+             "norm2", "router_w", "E", "r_top_k", "Q", "norm_topk", "defer_merge", "cand", "stats", "ids", "weights", "attn_splits",
+             "attn_partial", "attn_tickets", "cnt", "cnt_next", "timeout"]
+    fields = []
+    for n in order:
+        if n in _CHAIN_INTS:
+            fields.append((n, C.c_int32))
+        elif n == "a_slab_stride":
+            fields.append((n, C.c_int64))
+        elif n == "eps":
+            fields.append((n, C.c_float))
+        elif n in ("qkv", "o"):
+            fields.append((n, vp))
+        else:
+            fields += [(n, vp), (n + "_bytes", C.c_size_t)]
+    return fields
+
+
+class DecodeChainDesc(C.Structure):
+    _fields_ = _chain_fields()
+
+
+def decode_chain_desc(qkv, o, **kw):
+    """FerrumHipDecodeChainDesc from keywords: ints / eps by name, qkv / o as GptqLinear (or raw handles), every buffer as a torch
+    tensor (pointer and capacity taken from it), as a (pointer, bytes) pair, or left out (null, 0 bytes)."""
+    d = DecodeChainDesc()
+    d.qkv = getattr(qkv, "handle", qkv)
+    d.o = getattr(o, "handle", o)
+    d.head_dim, d.attn_splits = 128, 1
+    for k, v in kw.items():
+        if k in CHAIN_BUFFERS:
+            if v is None:
+                continue
+            ptr, nbytes = v if isinstance(v, tuple) else (v.data_ptr(), v.numel() * v.element_size())
+            setattr(d, k, ptr)
+            setattr(d, k + "_bytes", nbytes)
+        elif k in _CHAIN_INTS or k in ("eps", "a_slab_stride"):
+            setattr(d, k, v)
+        else:
+            raise TypeError(f"decode_chain_desc: unknown field {k}")
+    return d
+
+
+def decode_chain_supports(desc):
+    return bool(load_library().ferrum_hip_decode_chain_supports(C.byref(desc)))
+
+
+def decode_chain_counter_words():
+    return int(load_library().ferrum_hip_decode_chain_counter_words())
+
+
+def decode_chain(ctx, desc):
+    """The one-launch decode chain at op level (test and diagnosis entry): the runner's launcher behind capacity checks."""
+    _check(ctx.lib.ferrum_hip_decode_chain_f16(C.byref(desc), ctx.stream), "decode_chain")
+
+
+def gptq_shape_only(group_size, k, n):
+    """A GptqLinear of dims only (no device call), for decode_chain_supports."""
+    h = C.c_void_p()
+    _check(load_library().ferrum_hip_gptq_shape_only(C.byref(h), group_size, k, n), "gptq_shape_only")
+    return GptqLinear(h, k, n)
+
+
 class BlockAllocator:
     """Host `BlockAllocator` (ferrum-models/src/common/paged_pool.rs:106-365) via the C ABI."""
 

@@ -22,7 +22,18 @@ struct FerrumHipGptq {
     // expert_major_pair: [2][E] arrival counters + the give-up word of the merged gate_up → down launch
     unsigned* pair_arrive = nullptr;
     int pair_experts = 0;
+    bool shape_only = false;            // ferrum_hip_gptq_shape_only: k / n / G and nothing on the device
 };
+
+namespace fh {
+const W4Device* gptq_device(const FerrumHipGptq* h) { return &h->dev; }
+bool gptq_is_shape_only(const FerrumHipGptq* h) { return h->shape_only; }
+}
+
+// Every entry that computes passes its handle(s) through this, behind its null check: a handle made by
+// ferrum_hip_gptq_shape_only (or one whose upload never happened) has nothing a kernel could read.
+#define FH_REQUIRE_WEIGHTS(h, what) \
+    FH_REQUIRE(!(h)->shape_only && ((h)->dev.qw || (h)->dev.f16t), what ": the handle carries no weights (shape-only)")
 
 extern "C" {
 
@@ -90,6 +101,20 @@ int ferrum_hip_gptq_load_stacked(FerrumHipGptq** handle, const int32_t* const* q
     return 0;
 }
 
+// A handle that carries a projection's dims and no weights (no device call): what the shape predicates
+// (ferrum_hip_decode_chain_supports) are asked with before weights exist.  num_experts is 0 and the weight pointer null; every
+// entry that computes refuses it by name (FH_REQUIRE_WEIGHTS), the stack entries included.
+int ferrum_hip_gptq_shape_only(FerrumHipGptq** handle, int group_size, int k, int n) {
+    FH_REQUIRE(handle, "gptq_shape_only: null argument");
+    if (int rc = check_gptq_args(4, group_size, k, n)) return rc;
+    auto* g = new FerrumHipGptq();
+    g->dev.k = k; g->dev.n = n; g->dev.n64 = (n + 63) / 64; g->dev.G = k / 128;
+    g->dev.num_experts = 0;
+    g->shape_only = true;
+    *handle = g;
+    return 0;
+}
+
 // Act-order weights: the entry points read gathered input rows x'[r][j] = x[r][perm[j]] (`rows` input rows of K columns;
 // cuda/quant.rs:434).  The scratch grows outside of graph capture only (first call with more rows); an outgrown buffer stays
 // alive with the handle, because a graph captured at the smaller size holds its address.
@@ -136,6 +161,7 @@ int ferrum_hip_gptq_info(const FerrumHipGptq* g, int* k, int* n, int* num_expert
 int ferrum_hip_gptq_linear_forward_f16(const FerrumHipGptq* handle, const void* in, void* out, int m,
                                        FerrumHipWorkspace* ws, void* stream) {
     FH_REQUIRE(handle && (m == 0 || (in && out)), "gptq_linear_forward: null argument");
+    FH_REQUIRE_WEIGHTS(handle, "gptq_linear_forward");
     FH_REQUIRE(handle->dev.num_experts == 1, "gptq_linear_forward: handle is an expert stack");
     const __half* x = nullptr;
     if (int rc = gathered_input(handle, in, m, ST(stream), &x)) return rc;
@@ -148,6 +174,7 @@ int ferrum_hip_gptq_linear_slabs_f16(const FerrumHipGptq* handle, const void* x,
                                      int* S_inout, int* rows_pad_out, int* n_pad_out, void* stream) {
     FH_REQUIRE(handle && S_inout && rows_pad_out && n_pad_out && (m == 0 || (x && slabs)), "gptq_linear_slabs: null argument");
     FH_REQUIRE(form >= 0 && form <= 2, "gptq_linear_slabs: unknown form %d (0 skinny, 1 LDS-shared activations, 2 64-row tiles)", form);
+    FH_REQUIRE_WEIGHTS(handle, "gptq_linear_slabs");
     const W4Device& w = handle->dev;
     FH_REQUIRE(w.num_experts == 1 && w.qw && !w.f16t, "gptq_linear_slabs: handle is not a single INT4 projection");
     FH_REQUIRE(!w.perm, "gptq_linear_slabs: act-order weights (the runner's producers write the gathered rows themselves)");
@@ -166,13 +193,14 @@ int ferrum_hip_gptq_linear_forward_fused_tail_f16(const FerrumHipGptq* handle, c
                                                   void* out, int m, FerrumHipWorkspace* ws, void* stream) {
     FH_REQUIRE(handle && (m == 0 || (down && weights && residual_in && residual_out && ln_w && out)), "gptq_linear_forward_fused_tail: null argument");
     FH_REQUIRE(m == 0 || residual_in != residual_out, "gptq_linear_forward_fused_tail: residual_in == residual_out (every workgroup reads, one writes)");
+    FH_REQUIRE_WEIGHTS(handle, "gptq_linear_forward_fused_tail");
     FH_REQUIRE(handle->dev.num_experts == 1, "gptq_linear_forward_fused_tail: handle is an expert stack");
     const FusedCombineNorm fa{CH(down), weights, CH(residual_in), H(residual_out), CH(ln_w), eps, top_k};
     return w4_gemm_dense(handle->dev, nullptr, H(out), m, ws ? ws->ptr : nullptr, ws ? ws->bytes : 0, ST(stream), &fa);
 }
 
 int ferrum_hip_gptq_linear_can_fuse_tail(const FerrumHipGptq* handle, int m) {
-    return handle && handle->dev.num_experts == 1 && w4_gemm_dense_can_fuse_combine_norm(handle->dev, m) ? 1 : 0;
+    return handle && !handle->shape_only && handle->dev.num_experts == 1 && w4_gemm_dense_can_fuse_combine_norm(handle->dev, m) ? 1 : 0;
 }
 
 int ferrum_hip_moe_gemm_phase_f16(const FerrumHipGptq* stack, const void* input, const int32_t* sorted_token_ids,
@@ -181,6 +209,7 @@ int ferrum_hip_moe_gemm_phase_f16(const FerrumHipGptq* stack, const void* input,
                                   void* stream) {
     FH_REQUIRE(stack && input && sorted_token_ids && expert_ids && num_tokens_past_padded && output,
                "moe_gemm_phase: null argument");
+    FH_REQUIRE_WEIGHTS(stack, "moe_gemm_phase");
     if (moe_block_size != 16 && moe_block_size != 32 && moe_block_size != 64 && moe_block_size != 96 && moe_block_size != 128) {
         fh::set_error("moe_gemm_phase: moe_block_size=%d unsupported (16, 32, 64, 96 or 128)", moe_block_size);
         return FERRUM_HIP_UNSUPPORTED;
@@ -206,6 +235,7 @@ int ferrum_hip_moe_gemm_phase_inline_align_f16(const FerrumHipGptq* stack, const
                                                int num_experts, int top_k, int max_blocks, int fused_silu_mul,
                                                void* stream) {
     FH_REQUIRE(stack && input && expert_ids_per_pair && output, "moe_gemm_phase_inline_align: null argument");
+    FH_REQUIRE_WEIGHTS(stack, "moe_gemm_phase_inline_align");
     FH_REQUIRE(top_k >= 1, "moe_gemm_phase_inline_align: top_k=%d", top_k);
     FH_REQUIRE(!fused_silu_mul || stack->dev.fused_gate_up, "moe_gemm_phase_inline_align: fused epilogue needs a stack loaded with fuse_gate_up");
     FH_REQUIRE(fused_silu_mul || !stack->dev.fused_gate_up, "moe_gemm_phase_inline_align: stack was loaded with fuse_gate_up; plain output is column-permuted");
@@ -220,6 +250,7 @@ int ferrum_hip_moe_gemm_phase_expert_major_f16(const FerrumHipGptq* stack, const
                                                const int32_t* expert_ids_per_pair, void* output, int prob_m,
                                                int num_experts, int top_k, int fused_silu_mul, void* stream) {
     FH_REQUIRE(stack && input && expert_ids_per_pair && output, "moe_gemm_phase_expert_major: null argument");
+    FH_REQUIRE_WEIGHTS(stack, "moe_gemm_phase_expert_major");
     FH_REQUIRE(top_k >= 1 && num_experts >= 1, "moe_gemm_phase_expert_major: top_k=%d num_experts=%d", top_k, num_experts);
     FH_REQUIRE(!fused_silu_mul || stack->dev.fused_gate_up, "moe_gemm_phase_expert_major: fused epilogue needs a stack loaded with fuse_gate_up");
     FH_REQUIRE(fused_silu_mul || !stack->dev.fused_gate_up, "moe_gemm_phase_expert_major: stack was loaded with fuse_gate_up; plain output is column-permuted");
@@ -234,6 +265,8 @@ int ferrum_hip_moe_gemm_phase_expert_major_pair_f16(FerrumHipGptq* gate_up_stack
                                                     const int32_t* expert_ids_per_pair, void* act_out, void* output, int prob_m,
                                                     int num_experts, int top_k, void* stream) {
     FH_REQUIRE(gate_up_stack && down_stack && input && expert_ids_per_pair && act_out && output, "moe_gemm_phase_expert_major_pair: null argument");
+    FH_REQUIRE_WEIGHTS(gate_up_stack, "moe_gemm_phase_expert_major_pair");
+    FH_REQUIRE_WEIGHTS(down_stack, "moe_gemm_phase_expert_major_pair");
     FH_REQUIRE(top_k >= 1 && num_experts >= 1, "moe_gemm_phase_expert_major_pair: top_k=%d num_experts=%d", top_k, num_experts);
     FH_REQUIRE(gate_up_stack->dev.fused_gate_up && !down_stack->dev.fused_gate_up,
                "moe_gemm_phase_expert_major_pair: gate_up stack must be loaded with fuse_gate_up, the down stack without");
@@ -283,6 +316,7 @@ int ferrum_hip_moe_gemm_phase_merge_route_f16(const FerrumHipGptq* stack, const 
                                               int32_t* sorted_token_ids_out, int32_t* block_ids_out,
                                               int32_t* total_post_pad_out, void* stream) {
     FH_REQUIRE(stack && input && cand && stats && output && expert_ids_out && expert_weights_out, "merge_route: null argument");
+    FH_REQUIRE_WEIGHTS(stack, "merge_route");
     FH_REQUIRE(!fused_silu_mul || stack->dev.fused_gate_up, "merge_route: fused epilogue needs a stack loaded with fuse_gate_up");
     FH_REQUIRE(fused_silu_mul || !stack->dev.fused_gate_up, "merge_route: stack was loaded with fuse_gate_up; plain output is column-permuted");
     const __half* x_in = nullptr;
@@ -298,6 +332,7 @@ int ferrum_hip_moe_gemm_phase_merge_route_f16(const FerrumHipGptq* stack, const 
 int ferrum_hip_moe_gemm_phase_batched_f16(FerrumHipGptq* stack, const void* input, const int32_t* dispatches, int num_dispatches,
                                           void* output, int k, int fused_silu_mul, void* stream) {
     FH_REQUIRE(stack && (num_dispatches == 0 || (input && dispatches && output)), "gemm_phase_batched: null argument");
+    FH_REQUIRE_WEIGHTS(stack, "gemm_phase_batched");
     FH_REQUIRE(k == stack->dev.k, "gemm_phase_batched: k=%d but the stack was packed with K=%d", k, stack->dev.k);
     FH_REQUIRE(!fused_silu_mul || stack->dev.fused_gate_up, "gemm_phase_batched: fused epilogue needs a stack loaded with fuse_gate_up");
     FH_REQUIRE(fused_silu_mul || !stack->dev.fused_gate_up, "gemm_phase_batched: stack was loaded with fuse_gate_up; plain output is column-permuted");

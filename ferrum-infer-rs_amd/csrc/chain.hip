@@ -26,6 +26,9 @@
 // moe_combine_add_rmsnorm_kernel, w4_gemm_wgsplit_kernel<MT, 2> (K split over the 8 waves, LDS reduction in wave order),
 // paged_attn_kernel<128, true, 8> (fused QK-norm / RoPE / KV write, 8 KV-splitting waves merged in wave order),
 // add_rmsnorm_route_part_kernel (Q expert parts per token, in-launch ticket merge) — so the results are the same bits.
+// tests/test_chain_roles_gpu.py holds role A, the attention prologue (q rows, the new K / V slot) and role B's residual add to
+// that bit for bit, and every other stage to an element-wise bound from the device's own input to the stage (DESIGN.md §4,
+// "The decode chain role by role").
 #include "common.h"
 #include "kernels.h"
 #include "knobs.h"
@@ -218,13 +221,26 @@ __device__ __forceinline__ void chain_role_a(const ChainArgs& p, int row, unsign
             for (int j = 0; j < 8; j++) ss += (float)rv[j] * (float)rv[j];
         }
     }
-    // the stand-alone kernel sums four wave partials of 256 threads; rows of ≤ 2048 elements live in the first four waves
-    // here too, wider rows use all eight (same order: wave 0 … 7)
+    // the stand-alone kernels sum four wave partials of 256 threads; rows of ≤ 2048 elements live in the first four waves here
+    // too.  A row of ≤ 4096 elements (all that decode_chain_supports takes) is two vectors per thread there: thread t adds the
+    // squares of vector t + 256 onto its sum of vector t, element by element — so the upper four waves hand their vector to
+    // thread t − 256 through LDS and stay out of the sum: the same order, the same bits
+    const bool two_per_thread = nvec > 256 && nvec <= 512;
+    if (two_per_thread) {
+        half8* upper = reinterpret_cast<half8*>(smem + 64);          // [256] behind `red`
+        if (threadIdx.x >= 256) upper[threadIdx.x - 256] = v[0];
+        __syncthreads();
+        if (threadIdx.x + 256 < nvec) {
+            const half8 u = upper[threadIdx.x];
+#pragma unroll
+            for (int j = 0; j < 8; j++) ss += (float)u[j] * (float)u[j];
+        }
+    }
     ss = wave_reduce_sum(ss);
     if (lane == 0) red[wave] = ss;
     __syncthreads();
     float total = red[0] + red[1] + red[2] + red[3];
-    if (nvec > 256) total += red[4] + red[5] + red[6] + red[7];
+    if (nvec > 512) total += red[4] + red[5] + red[6] + red[7];
     const float inv = 1.0f / sqrtf(total / (float)H + p.eps);
 #pragma unroll
     for (int c = 0; c < CH; c++) {
@@ -993,6 +1009,8 @@ int decode_chain_f16(const DecodeChainDesc& d, hipStream_t stream) {
     form_hit(FORM_DECODE_CHAIN);
     if (a.attn_splits > 1) form_hit(FORM_CHAIN_ATTN_KV_SPLITS);
     if (a.qkv_wide) form_hit(FORM_CHAIN_QKV_WIDE);
+    if (a.qkv_half) form_hit(FORM_CHAIN_QKV_HALF);
+    if (a.o_half) form_hit(FORM_CHAIN_O_HALF);
     if (a.attn_splits > 1) {
         if (d.qkv->G / 8 == 2) hipLaunchKernelGGL((decode_chain_kernel<2, 4, false, true>), dim3(blocks), dim3(512), 0, stream, a);
         else hipLaunchKernelGGL((decode_chain_kernel<4, 4, false, true>), dim3(blocks), dim3(512), 0, stream, a);

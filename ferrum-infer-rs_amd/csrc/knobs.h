@@ -117,7 +117,9 @@ void reload_knobs();
     X(CHAIN_ATTN_KV_SPLITS, "chain_attn_kv_splits")   /* decode chain with several KV ranges per (sequence, kv head) in its attention role (ticket merge) */ \
     X(CHAIN_QKV_WIDE, "chain_qkv_wide")               /* decode chain with 128-column q|k|v blocks (the narrow ones + attention exceed the resident workgroups) */ \
     X(ROUTE_GEMM_TOPK, "route_gemm_topk")             /* prefill router: logits (MFMA) + softmax + top-k in one launch (moe_route_gemm_topk_kernel) */ \
-    X(MOE_PAIR_RANK_LISTS, "moe_pair_rank_lists")     /* the expert pair took the routing as per-part candidate lists: each tile ranks its own expert's candidates */
+    X(MOE_PAIR_RANK_LISTS, "moe_pair_rank_lists")     /* the expert pair took the routing as per-part candidate lists: each tile ranks its own expert's candidates */ \
+    X(CHAIN_QKV_HALF, "chain_qkv_half")               /* decode chain with 32-column q|k|v blocks (≤ 16 rows; neither this nor chain_qkv_wide: 64 columns) */ \
+    X(CHAIN_O_HALF, "chain_o_half")                   /* decode chain with 32-column o_proj blocks (≤ 16 rows, ≤ 2048 columns; otherwise 64) */
 
 enum Form : int {
 #define FH_FORM_ENUM(id, name) FORM_##id,

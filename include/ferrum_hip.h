@@ -197,6 +197,93 @@ int ferrum_hip_gptq_linear_forward_fused_tail_f16(const FerrumHipGptq* handle, c
                                                   const void* residual_in, void* residual_out, const void* ln_w, float eps, int top_k,
                                                   void* out, int m, FerrumHipWorkspace* ws, void* stream);
 int ferrum_hip_gptq_linear_can_fuse_tail(const FerrumHipGptq* handle, int m);
+
+/* ── the one-launch decode chain at op level (test and diagnosis entry; no reference counterpart) ─────────────────────
+ * [tail of the previous layer: combine + add + norm] → q|k|v → QK-norm / RoPE / KV write / attention → o_proj → add + norm +
+ * router + top-k as roles of ONE grid (csrc/chain.hip) — the launch the runner makes per decode layer, with every intermediate
+ * (norm1, qkv_out, attn_out, the two fp32 K parts of o_proj, res_b_out, norm2, the routing outputs) left in caller buffers
+ * so that each role can be compared with a reference of its own.  The entry calls the runner's launcher unchanged: the same
+ * kernel instantiations, FERRUM_HIP_CHAIN_* knobs and form counters.
+ *
+ * Every buffer pointer comes with its capacity in bytes.  Before anything is launched the entry holds each capacity (and each
+ * pointer's alignment) against what the launch touches, as derived from T, H, nq, nkv, E, Q, attn_splits and max_blocks, then
+ * reads kv_lens and the block tables back (a stream synchronisation: do not capture this entry) and requires
+ * 1 ≤ kv_len ≤ 16·max_blocks, a RoPE row per position and every block id of a context inside both pools.  A short buffer, a
+ * null that the form needs, or a value out of range → FERRUM_HIP_INVALID; a shape decode_chain_supports refuses →
+ * FERRUM_HIP_UNSUPPORTED; never a launch.
+ *
+ * Shapes taken (ferrum_hip_decode_chain_supports answers 1): head_dim 128, nq = 32, H 2048 or 4096, 1 ≤ T ≤ 128, nq / nkv ≤ 14,
+ * nkv ≤ 16, symmetric group-128 weights without act-order or bias; E = 0 (dense: Q = 1, role B is add + norm) or E ≤ 65520 with
+ * ceil(E / 16) divisible by Q ≤ 4, at most 8 tiles per part and r_top_k ≤ 8; attn_splits ≤ 16, and > 1 only with attn_partial
+ * and attn_tickets.
+ *
+ *   has_a      0: norm1 / res_a are inputs.  Otherwise role A makes them: E > 0 → res_a = fp16(res_in + Σ_j comb_w[t·top_k + j]·
+ *              down[t·top_k + j]); E = 0 → res_a = fp16(res_in + a_x) if a_x, else res_in + fp16(Σ_s a_slabs[s][t][·]) (a_S slabs,
+ *              a_slab_stride floats apart, rows a_ld floats apart); norm1 = rms_norm(res_a)·ln_in.
+ *   qkv, o     single-projection handles [H → (nq + 2·nkv)·128] and [nq·128 → H]; qkv_out [T, (nq + 2·nkv)·128] fp16.
+ *   attention  one new token per sequence at position kv_lens[t] − 1: its K / V (after qk_mode: 0 copy, 1 norm + half-split
+ *              RoPE, 2 half-split RoPE, 3 interleaved RoPE) are written into the pools, attn_out [T, nq·128] fp16.
+ *              block_tables [T, max_blocks]; cos_t / sin_t [positions, 64] f32; attn_partial [T·nkv·attn_splits][16][132] f32
+ *              and attn_tickets [T·nkv] (zero on entry, zero again after the launch) with attn_splits > 1.
+ *   o_part     [2][T][H] f32: the two K halves of o_proj; res_b_out = fp16(res_a + fp16(part 0 + part 1)), norm2 its norm·post_ln.
+ *   routing    router_w in the tiled layout of ferrum_hip_dense_repack_f16t ([ceil(E/16)·16, H]); defer_merge 0 → ids / weights
+ *              [T, r_top_k]; defer_merge 1 → cand [T·Q][8] (float logit, int32 id; unused slots −inf, 0x7fffffff) and stats
+ *              [T·Q][2] (max, Σexp) per (token, part).
+ *   cnt, cnt_next  two blocks of ferrum_hip_decode_chain_counter_words() words: cnt zero on entry, cnt_next zeroed by the launch
+ *              (callers alternate them).  timeout: one word, raised by a bounded in-launch wait that gave up (0 = every
+ *              hand-off completed). */
+typedef struct {
+    int32_t T, H, nq, nkv, head_dim;
+    int32_t has_a, top_k;
+    const void* down; size_t down_bytes;
+    const float* comb_w; size_t comb_w_bytes;
+    const void* res_in; size_t res_in_bytes;
+    const void* ln_in; size_t ln_in_bytes;
+    const float* a_slabs; size_t a_slabs_bytes;
+    int32_t a_S, a_ld;
+    int64_t a_slab_stride;
+    const void* a_x; size_t a_x_bytes;
+    float eps;
+    void* res_a; size_t res_a_bytes;
+    void* norm1; size_t norm1_bytes;
+    const FerrumHipGptq* qkv;
+    void* qkv_out; size_t qkv_out_bytes;
+    void* k_pool; size_t k_pool_bytes;
+    void* v_pool; size_t v_pool_bytes;
+    const int32_t* block_tables; size_t block_tables_bytes;
+    const uint32_t* kv_lens; size_t kv_lens_bytes;
+    const void* q_norm_w; size_t q_norm_w_bytes;
+    const void* k_norm_w; size_t k_norm_w_bytes;
+    const float* cos_t; size_t cos_t_bytes;
+    const float* sin_t; size_t sin_t_bytes;
+    int32_t qk_mode, max_blocks, sliding_window;
+    void* attn_out; size_t attn_out_bytes;
+    const FerrumHipGptq* o;
+    float* o_part; size_t o_part_bytes;
+    void* res_b_out; size_t res_b_out_bytes;
+    const void* post_ln; size_t post_ln_bytes;
+    void* norm2; size_t norm2_bytes;
+    const void* router_w; size_t router_w_bytes;
+    int32_t E, r_top_k, Q, norm_topk, defer_merge;
+    void* cand; size_t cand_bytes;
+    float* stats; size_t stats_bytes;
+    int32_t* ids; size_t ids_bytes;
+    float* weights; size_t weights_bytes;
+    int32_t attn_splits;
+    float* attn_partial; size_t attn_partial_bytes;
+    uint32_t* attn_tickets; size_t attn_tickets_bytes;
+    uint32_t* cnt; size_t cnt_bytes;
+    uint32_t* cnt_next; size_t cnt_next_bytes;
+    uint32_t* timeout; size_t timeout_bytes;
+} FerrumHipDecodeChainDesc;
+int ferrum_hip_decode_chain_f16(const FerrumHipDecodeChainDesc* desc, void* stream);
+int ferrum_hip_decode_chain_supports(const FerrumHipDecodeChainDesc* desc);
+int ferrum_hip_decode_chain_counter_words(void);
+/* A handle that carries a projection's dims and no weights (no device call): for asking ferrum_hip_decode_chain_supports before
+ * weights exist.  Every entry that computes — ferrum_hip_gptq_linear_* and every ferrum_hip_moe_gemm_phase_* — returns
+ * FERRUM_HIP_INVALID for it before reading anything else; ferrum_hip_gptq_info answers its dims (num_experts 0).  Freed with
+ * ferrum_hip_gptq_free. */
+int ferrum_hip_gptq_shape_only(FerrumHipGptq** handle, int group_size, int k, int n);
 /* One launch over the align-block routing arrays (moe_block_size 16: one-wave decode kernel; 32 or 64: LDS-tiled prefill
  * kernel; 96 or 128: the tall-tile prefill kernel — K must be a multiple of 256 — whose fp16 weights are (q − zero)·scale
  * rounded once, like the reference's own dequantisation; anything else → FERRUM_HIP_UNSUPPORTED): for every valid sorted id p,

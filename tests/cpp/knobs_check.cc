@@ -152,9 +152,9 @@ static void check_forms() {
         "route_fused", "route_gemm", "dense_slab_chain", "graph_capture", "graph_replay", "tp_allreduce_rccl",
         "tp_allreduce_loopback", "tp_allreduce_oneshot", "f16_dense_linear", "w4_fused_tail", "attn_resident", "w4_big", "gather_columns",
         "perm_producer", "moe_expert_major_pair", "decode_chain", "moe_deferred_merge", "dense_chain", "tp_allreduce_norm_fused", "chain_attn_kv_splits", "chain_qkv_wide", "route_gemm_topk",
-        "moe_pair_rank_lists"};
+        "moe_pair_rank_lists", "chain_qkv_half", "chain_o_half"};
     const int n = (int)(sizeof(NAMES) / sizeof(NAMES[0]));
-    CHECK(n == 45 && fh::FORM_COUNT == 45);
+    CHECK(n == 47 && fh::FORM_COUNT == 47);
     CHECK(fh::form_name(-1) == nullptr && fh::form_name(fh::FORM_COUNT) == nullptr);
     std::set<std::string> seen;
     for (int i = 0; i < fh::FORM_COUNT; i++) {

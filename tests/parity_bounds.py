@@ -512,3 +512,392 @@ def layer_norm_ref_tol(x, gamma, beta, eps):
     M = dim * EPS_F32 * np.abs(d).max(axis=-1, keepdims=True)
     tol = (EPS_F16 + EPS_F32) * np.abs(ref) + np.abs(n) * norm_scale_allowance(dim) + M * inv * np.abs(gam) + FLOOR_F16
     return ref, tol
+
+
+# ── decode attention of the one-launch chain (csrc/chain.hip, chain_role_attn) ───────────────────────────────────────────
+# A context is given in LOGICAL positions: K / V [columns·16, 128] are what the block table's columns name, in table order
+# (spare columns beyond the context included), fp16-valued.  The new token's K / V travel apart (the kernel patches them into
+# its fragments from LDS and must not read their pool slot).
+ATTN_SCALE = float(np.float32(1.0) / np.sqrt(np.float32(128.0)))      # the launcher's 1.0f / sqrtf(128)
+ATTN_CONTEXTS = (1, 2, 15, 16, 17, 31, 32, 33, 48, 129, 250, 256, 257, 300)
+ATTN_LONG_CONTEXTS = (1025, 1040, 2064)                               # beyond one 64-entry block-table window
+POISON_V = 6e4
+PLANT_MASS = (0.02, 0.20)
+
+
+def _cdiv(a, b):
+    return -(-a // b)
+
+
+def chain_attn_ranges(kv_len, window, splits):
+    """(win_lo, [(my_lo, my_hi)] per range) in block pairs, by the kernel's own split rule: the pairs [all_lo, all_hi) of the
+    masked context, range s = all_lo + n·s/NS … all_lo + n·(s + 1)/NS."""
+    pos0 = kv_len - 1
+    win_lo = max(0, pos0 + 1 - window) if window > 0 else 0
+    all_lo, all_hi = (win_lo // 16) // 2, (_cdiv(kv_len, 16) + 1) // 2
+    n = max(0, all_hi - all_lo)
+    return win_lo, [(all_lo + n * s // splits, all_lo + n * (s + 1) // splits) for s in range(splits)]
+
+
+def decode_attn_ref_tol(q, K, V, allowed, kv_len, window, splits=1, scale=ATTN_SCALE):
+    """float64 decode attention of R query rows over the `allowed` logical positions, and the element-wise bound of
+    chain_role_attn → (ref [R, 128], tol [R, 128], w [R, positions] the softmax masses, 0 outside `allowed`).
+
+        o = Σ_j w_j·v_j,  w = softmax(scale·q·k_j),      tol_d = 2^-11·|o_d| + ε·(Σ_j w_j|v_jd| + |o_d|) + S_d + 2^-24
+
+    q, K, V are the fp16 values the device used (K / V with the new token's row already in place).  ε is the sum of the relative
+    errors one probability w_j = p_j / l can carry, numerator and denominator counted separately, each term against the line
+    of chain_role_attn it covers (n keys allowed, it = ceil(pairs / 8) iterations of a wave at most, NS ranges):
+
+      2^-11                 `pf[j] = (_Float16)pv`: P is rounded to fp16 for the PV MFMA while `psum += pv` sums the unrounded
+                            fp32 values — numerator only;
+      2·δs                  `s0 = mfma(kf0[s], qf[s], s0)` ×4 and `sc[r] = s0[r] * p.scale`: 128 exact fp16 products accumulated in
+                            fp32 in the worst case one by one, δs_j = 128·2^-23·scale·Σ_i|q_i||k_ji| + 2^-24·|s_j| (the multiply),
+                            maximised over the row's keys; exp(s + δ) = exp(s)·(1 + δ): once in p_j, once (at most) in l;
+      2·(it + 3)·e_exp      `__expf` — on gfx950 v_mul_f32 by log2(e), then v_exp_f32 (1 ulp: 2^-23).  The product rounds once
+                            and log2(e) is itself an fp32 constant: 2·2^-24·|x| on the result; the argument `sc[j] - m_safe` rounds
+                            once more (2^-24·|x|): e_exp = 2^-23 + 3·2^-24·D with D the row's largest |s − m|.  A value meets its own
+                            exp, then one `alpha = __expf(m_run - m_safe)` per later iteration of its wave, `fw[w]` of the wave
+                            merge and `f` of the range merge (their arguments are differences of maxima of the same row: ≤ D) —
+                            at most it + 3 factors, in the numerator and in l alike;
+      2^-24·(2·(n + it + 2·8 + 2·NS) + 2)
+                            one 2^-24 per fp32 operation a value passes through, numerator and l each: the accumulation of PV
+                            (`o_acc = mfma(vfrag, pf, o_acc)`) and of `psum` / `l_run` over n terms in ANY order, `o_acc *= alpha`
+                            and `l_run * alpha` per iteration, multiply and add per wave of the LDS merge (`acc += lds_o·fw[w]`),
+                            multiply and add per range of the range merge; then `1.0f / Lm` and `ov[i] * inv`.
+
+    S_d = Σ_j min(w_j, 2^-14·w_max)·|v_jd| is absolute: p_j = exp(s_j − m_run) ≥ w_j / w_max whenever it is formed (m_run ≤ the
+    row's final maximum), so a p_j below the fp16 normal range 2^-14 — flushed by v_exp_f32 or coarsened to a subnormal by the
+    cast, in the numerator only — belongs to a key with w_j < 2^-14·w_max and is worth at most all of w_j.
+    2^-11·|o_d| is the fp16 store of the result, 2^-24 the fp16 floor.  One v_mfma_f32_16x16x32_f16 may add its 32 products with
+    a single rounding (an assumption nobody here has measured); the bound does not use it: n terms one by one cover both."""
+    q, K, V = np.asarray(q, np.float64), np.asarray(K, np.float64), np.asarray(V, np.float64)
+    allowed = np.asarray(allowed, bool)
+    idx = np.nonzero(allowed)[0]
+    Ka, Va = K[idx], V[idx]
+    s = scale * (q @ Ka.T)                                               # [R, n]
+    m = s.max(axis=1, keepdims=True)
+    e = np.exp(s - m)
+    wa = e / e.sum(axis=1, keepdims=True)
+    ref = wa @ Va
+    absw = wa @ np.abs(Va)
+    n = idx.size
+    _, ranges = chain_attn_ranges(kv_len, window, 1)
+    it = _cdiv(max(1, ranges[0][1] - ranges[0][0]), 8)
+    d_s = (128 * EPS_F32_SUM * scale * (np.abs(q) @ np.abs(Ka).T) + EPS_F32 * np.abs(s)).max(axis=1, keepdims=True)
+    e_exp = 2.0 ** -23 + 3 * EPS_F32 * (m - s.min(axis=1, keepdims=True))
+    eps = EPS_F16 + 2 * d_s + 2 * (it + 3) * e_exp + EPS_F32 * (2 * (n + it + 16 + 2 * splits) + 2)
+    small = np.minimum(wa, 2.0 ** -14 * wa.max(axis=1, keepdims=True)) @ np.abs(Va)
+    tol = EPS_F16 * np.abs(ref) + eps * (absw + np.abs(ref)) + small + FLOOR_F16
+    w = np.zeros((q.shape[0], K.shape[0]))
+    w[:, idx] = wa
+    return ref, tol, w
+
+
+def _exp32(x):
+    with np.errstate(under="ignore"):
+        return np.exp(np.asarray(x, np.float64)).astype(np.float32)
+
+
+ATTN_FAULTS = ("drop_last_key_of_range", "first_key_of_next_range_twice", "win_lo_one_low", "win_lo_one_high", "slot_past_kv_len",
+               "absent_second_block", "new_token_from_pool", "range_left_out", "stale_m", "neighbour_q", "window_not_reloaded")
+
+
+def chain_attn_emulate(q, K, V, k_new, v_new, kv_len, window, splits=1, scale=ATTN_SCALE, fault=None, fault_range=0):
+    """chain_role_attn restated in float32 / fp16, in the kernel's order: block pairs (32 keys) strided over 8 waves, per pair
+    four 32-term k-steps of QKᵀ (each k-step's exact sum added with one fp32 rounding — the single-rounding assumption of the
+    MFMA), `·scale`, mask, online softmax with fp32 `l` and fp16 P, one PV MFMA per pair; the 8 wave states merged in wave order;
+    the `splits` range states (m, l, o) merged in range order; reciprocal, multiply, fp16 store.  exp is float64 rounded to
+    fp32.  q [R, 128] the rows of ONE kv head, K / V logical positions (see above), k_new / v_new the new token's rows.
+
+    `fault` (ATTN_FAULTS) changes what the kernel would change: which logical positions are read and counted, which state
+    enters a merge.  fault_range picks the range for the faults that name one."""
+    assert fault is None or fault in ATTN_FAULTS
+    q32 = np.asarray(q, np.float32)
+    if fault == "neighbour_q":
+        q32 = np.roll(q32, 1, axis=0)
+    q64 = q32.astype(np.float64)
+    K, V = np.asarray(K, np.float64), np.asarray(V, np.float64)
+    R, NW = q32.shape[0], 8
+    pos0, nblocks = kv_len - 1, _cdiv(kv_len, 16)
+    win_lo, ranges = chain_attn_ranges(kv_len, window, splits)
+    win_eff = win_lo + {"win_lo_one_low": -1, "win_lo_one_high": 1}.get(fault, 0)
+    mult = np.ones(K.shape[0])
+    if fault == "drop_last_key_of_range":
+        mult[ranges[fault_range][1] * 32 - 1] = 0
+    if fault == "first_key_of_next_range_twice":
+        mult[ranges[fault_range + 1][0] * 32] = 2
+    ninf = np.float32(-np.inf)
+    states = []
+    for (my_lo, my_hi) in ranges:
+        bt_lo = 2 * my_lo
+        wm, wl, wo = np.full((NW, R), ninf), np.zeros((NW, R), np.float32), np.zeros((NW, R, 128), np.float32)
+        for wave in range(NW):
+            m_run, l_run, o = np.full(R, ninf), np.zeros(R, np.float32), np.zeros((R, 128), np.float32)
+            for pr in range(my_lo + wave, my_hi, NW):
+                pos = pr * 32 + np.arange(32)
+                blk = pos // 16
+                has = blk < nblocks
+                if fault == "absent_second_block":
+                    has = blk < K.shape[0] // 16
+                src_blk = np.where(has, blk, 2 * pr)                         # phys1 = phys0 where the pair has no second block
+                if fault == "window_not_reloaded":
+                    src_blk = bt_lo + (src_blk - bt_lo) % 64
+                src = src_blk * 16 + pos % 16
+                Kp, Vp = K[src].copy(), V[src].copy()
+                if fault != "new_token_from_pool" and pos[0] <= pos0 <= pos[-1]:
+                    Kp[pos0 - pos[0]], Vp[pos0 - pos[0]] = k_new, v_new
+                s = np.zeros((R, 32))
+                for ks in range(4):
+                    s = _fl32(s + q64[:, 32 * ks:32 * ks + 32] @ Kp[:, 32 * ks:32 * ks + 32].T)
+                ok = (pos <= pos0 + (1 if fault == "slot_past_kv_len" else 0)) & (pos >= win_eff)
+                if fault == "absent_second_block":
+                    ok = ok | ((blk >= nblocks) & has & (blk == 2 * pr + 1))
+                ok = ok & (mult[pos] > 0)
+                sc = np.where(ok[None, :], (s.astype(np.float32) * np.float32(scale)), ninf).astype(np.float32)
+                m_new = np.maximum(m_run, sc.max(axis=1))
+                m_safe = np.where(np.isneginf(m_new), np.float32(0), m_new)
+                with np.errstate(invalid="ignore"):
+                    alpha = np.where(np.isneginf(m_run), np.float32(0), _exp32(m_run - m_safe))
+                p = _exp32(sc - m_safe[:, None]) * mult[pos][None, :].astype(np.float32)
+                l_run = l_run * alpha + p.sum(axis=1, dtype=np.float32)
+                pf = p.astype(np.float16).astype(np.float64)
+                o = _fl32((o * alpha[:, None]).astype(np.float64) + pf @ Vp).astype(np.float32)
+                m_run = m_new
+            wm[wave], wl[wave], wo[wave] = m_run, l_run, o
+        M = wm.max(axis=0)
+        Ms = np.where(np.isneginf(M), np.float32(0), M)
+        L, acc = np.zeros(R, np.float32), np.zeros((R, 128), np.float32)
+        for w in range(NW):
+            fw = _exp32(wm[w] - Ms)
+            L = L + wl[w] * fw
+            acc = acc + wo[w] * fw[:, None]
+        states.append((M, L, acc))
+    if splits == 1:
+        M, L, acc = states[0]
+    else:
+        ms = np.stack([st[0] for st in states])
+        merged = [i for i in range(splits) if not (fault == "range_left_out" and i == fault_range)]
+        M = ms[merged].max(axis=0)
+        Ms = np.where(np.isneginf(M), np.float32(0), M)
+        L, acc = np.zeros(R, np.float32), np.zeros((R, 128), np.float32)
+        for i in merged:
+            m_i = ms[i - 1] if (fault == "stale_m" and i == fault_range) else ms[i]
+            f = _exp32(m_i - Ms)
+            L = L + states[i][1] * f
+            acc = acc + states[i][2] * f[:, None]
+    with np.errstate(divide="ignore"):
+        inv = np.where(L > 0, np.float32(1) / L, np.float32(0)).astype(np.float32)
+    with np.errstate(over="ignore", invalid="ignore"):
+        return (acc * inv[:, None]).astype(np.float16).astype(np.float32)
+
+
+def attn_edge_positions(kv_len, window, splits):
+    """The positions inside the mask (the new token apart) that a fault would lose or wrongly gain: position 0, win_lo, the
+    first and last key of every KV range (my_lo·32, my_hi·32 − 1), both sides of the last two 16-key block seams, pos0 − 1."""
+    pos0 = kv_len - 1
+    win_lo, ranges = chain_attn_ranges(kv_len, window, splits)
+    want = [0, win_lo, pos0 - 1]
+    for lo, hi in ranges:
+        if hi > lo:
+            want += [lo * 32, hi * 32 - 1]
+    for seam in ((pos0 // 16) * 16, (pos0 // 16 - 1) * 16):
+        want += [seam - 1, seam]
+    return sorted({p for p in want if win_lo <= p < pos0})
+
+
+def attn_poison_positions(kv_len, window, columns):
+    """Logical positions outside the mask that must not be counted: win_lo − 1, every slot ≥ kv_len of the last block, the
+    whole second block of an odd pair and every table column beyond the context, and the new token's own pool slot."""
+    pos0, nblocks = kv_len - 1, _cdiv(kv_len, 16)
+    win_lo, _ = chain_attn_ranges(kv_len, window, 1)
+    out = set(range(kv_len, columns * 16)) | {pos0}
+    if win_lo > 0:
+        out.add(win_lo - 1)
+    return sorted(out)
+
+
+def plant_context(rng, q, k_new, kv_len, window, splits, columns, scale=ATTN_SCALE):
+    """Logical K / V [columns·16, 128] (fp16-valued) of one (sequence, kv head) whose G query rows are q [G, 128] → dict(K, V,
+    edges, heads, poison).  Background N(0, 1).  Edge position i (attn_edge_positions) holds K = f16(β_h·q̂_h), h = i mod G, with
+    β_h solved so that each of the m_h keys planted for row h carries t_h = min(8 %, 60 % / m_h) of that row's softmax mass
+    against everything else the row sees (the other rows' planted keys and the new token included; four fixed-point rounds),
+    and V = ±2 in a sign pattern of its own.  Poison (attn_poison_positions): K = f16(γ·u), u the unit vector with the same product on every q̂ (pinv(q̂)·1) and γ such
+    that on EVERY row the key alone would outweigh the whole allowed context by e (> 50 % of the mass if counted), V = ±6e4."""
+    q = np.asarray(q, np.float64)
+    G, P = q.shape[0], columns * 16
+    pos0 = kv_len - 1
+    win_lo, _ = chain_attn_ranges(kv_len, window, 1)
+    K, V = f16r(rng.standard_normal((P, 128))).astype(np.float64), f16r(rng.standard_normal((P, 128))).astype(np.float64)
+    qn = np.linalg.norm(q, axis=1)
+    qhat = q / qn[:, None]
+    edges = attn_edge_positions(kv_len, window, splits)
+    heads = [i % G for i in range(len(edges))]
+    for p in edges:
+        V[p] = 2.0 * np.random.default_rng(7000 + p).choice([-1.0, 1.0], 128)
+    allowed = np.zeros(P, bool)
+    allowed[win_lo:kv_len] = True
+    Keff = K.copy()
+    Keff[pos0] = k_new
+    beta = np.zeros(G)
+    for _ in range(4):
+        for p, h in zip(edges, heads):
+            Keff[p] = f16r(beta[h] * qhat[h])
+        s = scale * (q @ Keff[allowed].T)                                # [G, n]
+        apos = np.nonzero(allowed)[0]
+        for h in range(G):
+            mine = np.isin(apos, [p for p, hh in zip(edges, heads) if hh == h])
+            m_h = int(mine.sum())
+            if m_h == 0:
+                continue
+            t = min(0.08, 0.6 / m_h)
+            logZ = np.logaddexp.reduce(s[h, ~mine]) if (~mine).any() else 0.0
+            beta[h] = (np.log(t / (1.0 - m_h * t)) + logZ) / (scale * qn[h])
+    for p, h in zip(edges, heads):
+        K[p] = f16r(beta[h] * qhat[h])
+    Keff[edges] = K[edges]
+    u = np.linalg.pinv(qhat) @ np.ones(G)                                 # q̂_h·u = 1 for every row (G ≤ 14 independent rows of 128)
+    u /= np.linalg.norm(u)
+    assert np.all(q @ u > 0), "a query row points away from the poison direction"
+    logZ = np.logaddexp.reduce(scale * (q @ Keff[allowed].T), axis=1)
+    gamma = float(((logZ + 1.0) / (scale * (q @ u))).max())
+    poison = attn_poison_positions(kv_len, window, columns)
+    for p in poison:
+        K[p] = f16r(gamma * u)
+        V[p] = POISON_V * np.where((np.arange(128) + p) % 2 == 0, 1.0, -1.0)
+    assert np.isfinite(K).all() and np.abs(K).max() < 6e4
+    return dict(K=K, V=V, edges=edges, heads=heads, poison=poison, allowed=allowed)
+
+
+def effective_kv(ctx, k_new, v_new, kv_len):
+    """K / V as the kernel sees them: the planted context with the new token's rows in place."""
+    K, V = ctx["K"].copy(), ctx["V"].copy()
+    K[kv_len - 1], V[kv_len - 1] = k_new, v_new
+    return K, V
+
+
+# ── routing without logits (role B of the chain never stores them) ────────────────────────────────────────────────────────
+def route_logits_ref_tol(norm2, router_w):
+    """float64 router logits L = norm2·Wᵀ from the DEVICE's norm2 rows and the fp16 router rows, and the fp32 GEMM bound
+    gemm_tolerance(…, k = H, folded = False, out_f32 = True) → (L [T, E], tol_L [T, E])."""
+    ref, absdot = gemm_refs(norm2, router_w)
+    return ref, gemm_tolerance(ref, absdot, np.asarray(norm2).shape[1], False, out_f32=True)
+
+
+def assert_route_selection(L, tol, ids, weights, norm_topk, what="routing"):
+    """ids / weights [T, K] of the merged routing against float64 logits L ± tol.
+
+      selection   no unchosen expert u may have L_u − tol_u > L_c + tol_c for a chosen c;
+      rank order  consecutive chosen experts a (rank r), b (rank r + 1): not L_b − tol_b > L_a + tol_a;
+      exact ties  experts whose router rows are duplicates give bit-identical logits: callers pass them through `tie_groups`
+                  to assert_route_ties;
+      weights     against softmax(L) over all E, renormalised over the device's chosen set when norm_topk:
+                  |w − ref| ≤ ref·(2·max tol_L + (E + 8)·2^-24) — every exponent moves by ≤ tol_L (numerator) and the sum by ≤ max
+                  tol_L (denominator); the fp32 sum of E exps in any order, the exp, the reciprocal and the products: (E + 8)·2^-24.
+    Returns the largest weight err/tol."""
+    L, tol = np.asarray(L, np.float64), np.asarray(tol, np.float64)
+    ids, weights = np.asarray(ids), np.asarray(weights, np.float64)
+    T, E = L.shape
+    K = ids.shape[1]
+    worst = 0.0
+    for t in range(T):
+        c = ids[t]
+        assert len(set(c.tolist())) == K and c.min() >= 0 and c.max() < E, f"{what}: token {t} ids {c.tolist()}"
+        un = np.setdiff1d(np.arange(E), c)
+        if un.size:
+            u = un[np.argmax(L[t, un] - tol[t, un])]
+            lo = c[np.argmin(L[t, c] + tol[t, c])]
+            assert not (L[t, u] - tol[t, u] > L[t, lo] + tol[t, lo]), \
+                f"{what}: token {t}: unchosen expert {u} (L {L[t, u]!r}) beats chosen {lo} (L {L[t, lo]!r}) beyond both tolerances"
+        for r in range(K - 1):
+            a, b = c[r], c[r + 1]
+            assert not (L[t, b] - tol[t, b] > L[t, a] + tol[t, a]), f"{what}: token {t}: rank {r + 1} (expert {b}) above rank {r} (expert {a})"
+        p = np.exp(L[t] - L[t].max())
+        p /= p.sum()
+        ref = p[c] / p[c].sum() if norm_topk else p[c]
+        wtol = ref * (2 * tol[t].max() + (E + 8) * EPS_F32)
+        err = np.abs(weights[t] - ref)
+        assert np.all(err <= wtol), f"{what}: token {t} combine weights {weights[t].tolist()} against {ref.tolist()} (err/tol {float((err / wtol).max()):.3g})"
+        worst = max(worst, float((err / wtol).max()))
+    return worst
+
+
+def assert_route_ties(ids, tie_groups, what="routing"):
+    """tie_groups: lists of expert ids with bit-identical logits (duplicated router rows).  Of a tied group the chosen members
+    must be its LOWEST ids, in id order, at consecutive ranks.  Returns the number of tokens whose top-k boundary cuts a group."""
+    cut = 0
+    for t, c in enumerate(np.asarray(ids).tolist()):
+        for g in tie_groups:
+            g = sorted(g)
+            chosen = [e for e in c if e in g]
+            assert chosen == g[:len(chosen)], f"{what}: token {t}: tied group {g} chose {chosen}"
+            if chosen:
+                r = [c.index(e) for e in chosen]
+                assert r == list(range(r[0], r[0] + len(r))), f"{what}: token {t}: tied experts {chosen} at ranks {r}"
+            cut += 0 < len(chosen) < len(g)
+    return cut
+
+
+def route_beats(lj, ij, l, i):
+    return lj > l or (lj == l and ij < i)
+
+
+def assert_route_lists(L, tol, cand_logit, cand_id, stats, Q, top_k, what="candidate lists"):
+    """The per-part candidate lists of defer_merge: cand_logit / cand_id [T, Q, 8], stats [T, Q, 2] (max, Σexp); part q owns
+    experts [q, q + 1)·EQ cut at E, EQ = ceil(E / 16) / Q · 16, and lists its best keep = min(top_k, EQ).
+
+      order     each list is sorted by route_beats on its own logit bits;
+      values    every listed logit within tol_L of float64;
+      coverage  no unlisted expert u of the part with L_u − tol_u > L_last + tol_last;
+      unused    slots ≥ keep hold (0x7fffffff, −inf);
+      stats     max equals the first listed logit bit for bit; Σexp = Σ_e exp(l_e − max) within
+                Σexp·((EQ + 8)·2^-24 + 2·max tol_L): every exponent and the maximum move by ≤ tol_L; EQ exps summed in fp32 in any
+                order, the exp and the subtraction: (EQ + 8)·2^-24."""
+    L, tol = np.asarray(L, np.float64), np.asarray(tol, np.float64)
+    T, E = L.shape
+    EQ = _cdiv(E, 16) // Q * 16
+    keep = min(top_k, EQ)
+    cl, ci, st = np.asarray(cand_logit, np.float32), np.asarray(cand_id), np.asarray(stats, np.float32)
+    for t in range(T):
+        for qq in range(Q):
+            own = np.arange(qq * EQ, min(E, (qq + 1) * EQ))
+            n_l = min(keep, own.size)
+            ids, lg = ci[t, qq], cl[t, qq]
+            assert np.all(ids[n_l:] == 0x7fffffff) and np.all(np.isneginf(lg[n_l:])), f"{what}: token {t} part {qq}: unused slots {ids.tolist()} {lg.tolist()}"
+            listed = ids[:n_l]
+            assert len(set(listed.tolist())) == n_l and np.all(np.isin(listed, own)), f"{what}: token {t} part {qq}: ids {listed.tolist()}"
+            for r in range(n_l - 1):
+                assert route_beats(lg[r], int(ids[r]), lg[r + 1], int(ids[r + 1])), f"{what}: token {t} part {qq}: slots {r}, {r + 1} out of order"
+            assert np.all(np.abs(lg[:n_l].astype(np.float64) - L[t, listed]) <= tol[t, listed]), f"{what}: token {t} part {qq}: a listed logit outside tol_L"
+            un = np.setdiff1d(own, listed)
+            if un.size and n_l:
+                u, last = un[np.argmax(L[t, un] - tol[t, un])], listed[-1]
+                assert not (L[t, u] - tol[t, u] > L[t, last] + tol[t, last]), f"{what}: token {t} part {qq}: unlisted expert {u} beats the last listed {last}"
+            assert st[t, qq, 0].tobytes() == lg[0].tobytes(), f"{what}: token {t} part {qq}: stats.max {st[t, qq, 0]!r} is not the first listed logit {lg[0]!r}"
+            ref = np.exp(L[t, own] - L[t, own].max()).sum()
+            stol = ref * ((EQ + 8) * EPS_F32 + 2 * tol[t, own].max())
+            assert abs(float(st[t, qq, 1]) - ref) <= stol, f"{what}: token {t} part {qq}: Σexp {st[t, qq, 1]!r} against {ref!r} (tol {stol:.3g})"
+
+
+# The attention cases of tests/test_chain_roles_gpu.py (the CPU self-test runs the restatement through the same list):
+# name → (nkv, attn_splits, sliding_window, contexts — row t of the launch holds contexts[t % len]).
+def _window_contexts(w):
+    return tuple(n for n in (w - 1, w, w + 1) if n >= 1) + (300,)
+
+
+ATTN_CASES = {
+    "g8-unsplit": (4, 1, 0, ATTN_CONTEXTS),
+    "g8-5-ranges": (4, 5, 0, ATTN_CONTEXTS),
+    "g8-16-ranges": (4, 16, 0, ATTN_CONTEXTS),
+    "g4-5-ranges": (8, 5, 0, ATTN_CONTEXTS),
+    "g4-unsplit": (8, 1, 0, ATTN_CONTEXTS),
+    "g2-unsplit": (16, 1, 0, ATTN_CONTEXTS),
+    "g2-16-ranges": (16, 16, 0, ATTN_CONTEXTS),
+    "window-1": (4, 1, 1, _window_contexts(1)),
+    "window-16-5-ranges": (4, 5, 16, _window_contexts(16)),
+    "window-17": (4, 1, 17, _window_contexts(17)),
+    "window-150-5-ranges": (4, 5, 150, _window_contexts(150)),
+    "window-150-g4-16-ranges": (8, 16, 150, _window_contexts(150)),
+    "long-unsplit": (4, 1, 0, ATTN_LONG_CONTEXTS),
+    "long-5-ranges": (4, 5, 0, ATTN_LONG_CONTEXTS),
+}

@@ -405,3 +405,167 @@ def test_dense_decode_exports_reject_bad_arguments_on_the_host(pkg):
         assert call() == 2, name
         assert word in lib.ferrum_hip_last_error(), (name, lib.ferrum_hip_last_error())
     assert lib.ferrum_hip_gptq_linear_can_fuse_tail(None, 1) == 0
+
+
+# ── the op-level decode-chain entry: symbols, the shape predicate and the capacity checks, all on the host ─────────────────
+def _chain_shape(be, H=2048, nq=32, nkv=4, T=4, E=128, Q=4, r_top_k=8, attn_splits=1, group=128, **kw):
+    """A descriptor over weightless handles with every buffer the form touches at a fake, aligned, never-dereferenced address and
+    exactly the capacity the launch needs (restated here from the roles' index ranges, not read from the library)."""
+    qkv = be.gptq_shape_only(group, H, (nq + 2 * nkv) * 128)
+    o = be.gptq_shape_only(group, nq * 128, H)
+    f = dict(T=T, H=H, nq=nq, nkv=nkv, E=E, Q=Q, r_top_k=r_top_k, attn_splits=attn_splits, has_a=1, top_k=8, eps=1e-6, qk_mode=1,
+             max_blocks=5, sliding_window=0, norm_topk=1, defer_merge=0, a_S=0, a_ld=0, a_slab_stride=0)
+    dense_form = kw.pop("dense_form", "rows")
+    f.update(kw)
+    T, H, E, Q = f["T"], f["H"], f["E"], f["Q"]
+    words = be.decode_chain_counter_words()
+    row = T * H * 2
+    need = dict(res_in=row, ln_in=H * 2, res_a=row, norm1=row, qkv_out=T * (nq + 2 * nkv) * 128 * 2, q_norm_w=256, k_norm_w=256,
+                cos_t=256, sin_t=256, k_pool=nkv * 4096, v_pool=nkv * 4096, block_tables=T * f["max_blocks"] * 4, kv_lens=T * 4,
+                attn_out=T * nq * 256, o_part=2 * T * H * 4, res_b_out=row, post_ln=H * 2, norm2=row, cnt=words * 4, cnt_next=words * 4,
+                timeout=4)
+    if E > 0:
+        need.update(down=T * f["top_k"] * H * 2, comb_w=T * f["top_k"] * 4, router_w=(E + 15) // 16 * 16 * H * 2)
+        need.update(dict(cand=T * Q * 64, stats=T * Q * 8) if f["defer_merge"] else dict(ids=T * f["r_top_k"] * 4, weights=T * f["r_top_k"] * 4))
+    elif dense_form == "rows":
+        need.update(a_x=row)
+    else:
+        f.update(a_S=3, a_ld=H + 64, a_slab_stride=T * (H + 64) + 32)
+        need.update(a_slabs=(2 * f["a_slab_stride"] + (T - 1) * f["a_ld"] + H) * 4)
+    if f["attn_splits"] > 1:
+        need.update(attn_partial=T * nkv * f["attn_splits"] * 16 * 132 * 4, attn_tickets=T * nkv * 4)
+    bufs = {n: (0x10000 * (i + 1), b) for i, (n, b) in enumerate(sorted(need.items()))}
+    return (qkv, o), f, bufs
+
+
+def test_decode_chain_entry_symbols_and_struct_order(pkg):
+    out = subprocess.check_output(["nm", "-D", "--defined-only", pkg.LIB_PATH], text=True)
+    exported = set(line.split()[-1] for line in out.splitlines() if " T " in line)
+    assert {"ferrum_hip_decode_chain_f16", "ferrum_hip_decode_chain_supports", "ferrum_hip_decode_chain_counter_words"} <= exported
+    from ferrum_infer_rs_amd import backend as be
+    hdr = re.sub(r"/\*.*?\*/", "", open(os.path.join(ROOT, "include", "ferrum_hip.h")).read(), flags=re.S)
+    body = re.search(r"typedef struct\s*\{([^}]*)\}\s*FerrumHipDecodeChainDesc;", hdr).group(1)
+    names = []
+    for decl in body.split(";"):
+        decl = re.sub(r"\s+", " ", decl.strip())
+        if decl:
+            first, *rest = decl.split(",")
+            names += [first.split()[-1]] + [r.strip() for r in rest]
+    assert [n for n, _ in be.DecodeChainDesc._fields_] == names                # the ctypes mirror follows the header
+    # 56 line slots of 64 words + 16 kv heads × 4 replicas, and the route granules of 128 tokens × 4 parts × 10 × 2 words
+    assert be.decode_chain_counter_words() == (56 + 4 * 16) * 64 + 128 * 4 * 10 * 2
+
+
+def test_decode_chain_supports_answers_by_shape(pkg):
+    """ferrum_hip_decode_chain_supports over weightless handles (nothing touches a device): the table of the shapes the chain
+    takes and refuses, as decode_chain_supports (csrc/chain.hip) states them."""
+    from ferrum_infer_rs_amd import backend as be
+    table = {
+        "H 2048 MoE": (dict(), True),
+        "H 4096 MoE": (dict(H=4096), True),
+        "H 4096 dense": (dict(H=4096, nkv=8, E=0, Q=1), True),
+        "H 2048 nkv 16": (dict(nkv=16), True),
+        "T 128": (dict(T=128), True),
+        "T 129": (dict(T=129), False),
+        "H 1024": (dict(H=1024), False),
+        "H 8192": (dict(H=8192), False),
+        "nq 16": (dict(nq=16), False),
+        "nq 64": (dict(nq=64, nkv=8), False),
+        "GQA group 16": (dict(nkv=2), False),
+        "head_dim 64": (dict(head_dim=64), False),
+        "E 60 Q 4": (dict(E=60, Q=4, r_top_k=4), True),
+        "E 24 Q 2": (dict(E=24, Q=2, r_top_k=4), True),
+        "E 128 Q 3 (8 tiles)": (dict(E=128, Q=3), False),
+        "E 48 Q 2 (3 tiles)": (dict(E=48, Q=2), False),
+        "E 128 Q 5": (dict(E=128, Q=5), False),
+        "r_top_k 9": (dict(r_top_k=9), False),
+        "dense Q 2": (dict(E=0, Q=2), False),
+        "attn_splits 16": (dict(attn_splits=16), True),
+        "attn_splits 17": (dict(attn_splits=17), False),
+        "group 256": (dict(group=256), True),                   # (the packed layout is in 128-wide groups whatever the checkpoint's)
+    }
+    for name, (kw, want) in table.items():
+        hs, f, bufs = _chain_shape(be, **kw)
+        assert be.decode_chain_supports(be.decode_chain_desc(*hs, **f, **bufs)) == want, name
+    hs, f, bufs = _chain_shape(be, attn_splits=5)
+    assert be.decode_chain_supports(be.decode_chain_desc(*hs, **f, **bufs))
+    for missing in ("attn_partial", "attn_tickets", "o_part"):
+        assert not be.decode_chain_supports(be.decode_chain_desc(*hs, **f, **{k: v for k, v in bufs.items() if k != missing})), missing
+    d = be.decode_chain_desc(*hs, **f, **bufs)
+    d.qkv = None
+    assert not be.decode_chain_supports(d)
+    hs2, _, _ = _chain_shape(be, H=4096)
+    assert not be.decode_chain_supports(be.decode_chain_desc(hs2[0], hs[1], **f, **bufs))      # q|k|v of another hidden size
+
+
+def test_decode_chain_entry_refuses_short_buffers_before_any_launch(pkg):
+    """Per form, every buffer the launch touches: one byte short, null, or misaligned → FERRUM_HIP_INVALID naming the buffer.
+    With exactly the needed capacities every check passes and the call stops at the weightless handles — the pointers here are
+    fake, so reaching a launch (or the device read-back of kv_lens) is not survivable: the order of the checks is under test."""
+    from ferrum_infer_rs_amd import backend as be
+    lib = pkg.load_library()
+    forms = {
+        "moe merged": dict(),
+        "moe deferred, 5 ranges": dict(defer_merge=1, attn_splits=5, T=3),
+        "moe H 4096 top_k 10": dict(H=4096, top_k=10, T=17),
+        "moe no tail, no rope": dict(has_a=0, qk_mode=0),
+        "dense rows": dict(H=4096, nkv=8, E=0, Q=1, qk_mode=2),
+        "dense slabs": dict(H=4096, nkv=8, E=0, Q=1, dense_form="slabs", T=33),
+    }
+    call = lambda d: lib.ferrum_hip_decode_chain_f16(C.byref(d), None)
+    checked = 0
+    for form, kw in forms.items():
+        hs, f, bufs = _chain_shape(be, **kw)
+        if not f["has_a"]:
+            bufs = {k: v for k, v in bufs.items() if k not in ("down", "comb_w", "res_in", "ln_in")}
+        if f["qk_mode"] != 1:
+            bufs = {k: v for k, v in bufs.items() if k not in ("q_norm_w", "k_norm_w")}
+        if f["qk_mode"] == 0:
+            bufs = {k: v for k, v in bufs.items() if k not in ("cos_t", "sin_t")}
+        assert call(be.decode_chain_desc(*hs, **f, **bufs)) == 2, form
+        assert b"shape-only handle" in lib.ferrum_hip_last_error(), (form, lib.ferrum_hip_last_error())
+        for name, (ptr, nbytes) in bufs.items():
+            for what, bad in (("holds", (ptr, nbytes - 1)), ("null", (0, nbytes)), ("aligned", (ptr + 2, nbytes))):
+                if name in ("o_part", "attn_partial", "attn_tickets", "a_x", "a_slabs") and what == "null":
+                    continue                                  # (nulls the shape predicate itself refuses — rc 3; a null a_x selects the slab form)
+                assert call(be.decode_chain_desc(*hs, **f, **{**bufs, name: bad})) == 2, (form, name, what)
+                err = lib.ferrum_hip_last_error()
+                assert name.encode() in err and what.encode() in err, (form, name, what, err)
+                checked += 1
+    assert checked > 300
+    hs, f, bufs = _chain_shape(be)
+    assert call(be.decode_chain_desc(*hs, **f, **{**bufs, "cnt_next": bufs["cnt"]})) == 2 and b"cnt == cnt_next" in lib.ferrum_hip_last_error()
+    assert call(be.decode_chain_desc(*hs, **{**f, "H": 1024}, **bufs)) == 3
+    assert call(be.decode_chain_desc(*hs, **{**f, "qk_mode": 4}, **bufs)) == 2
+    assert lib.ferrum_hip_decode_chain_f16(None, None) == 2
+
+
+def test_weightless_handle_is_refused_by_every_computing_entry(pkg):
+    """A ferrum_hip_gptq_shape_only handle carries dims and no weights: every GPTQ entry that would launch — the single-projection
+    ones and every expert-stack phase — returns FERRUM_HIP_INVALID naming the reason, before anything else is read (the other
+    pointers here are fake and never dereferenced); can_fuse_tail answers 0, info answers the dims."""
+    from ferrum_infer_rs_amd import backend as be
+    lib = pkg.load_library()
+    lin, lin2 = be.gptq_shape_only(128, 2048, 512), be.gptq_shape_only(128, 256, 2048)      # (they free their handles when they go)
+    h, h2 = lin.handle, lin2.handle
+    one, two = C.c_void_p(4096), C.c_void_p(8192)
+    s, rp, npad = C.c_int(1), C.c_int(0), C.c_int(0)
+    f = C.c_float(1e-6)
+    calls = {
+        "gptq_linear_forward": lambda: lib.ferrum_hip_gptq_linear_forward_f16(h, one, one, 1, None, None),
+        "gptq_linear_slabs": lambda: lib.ferrum_hip_gptq_linear_slabs_f16(h, one, one, C.c_size_t(1 << 20), 1, 0, C.byref(s), C.byref(rp), C.byref(npad), None),
+        "gptq_linear_forward_fused_tail": lambda: lib.ferrum_hip_gptq_linear_forward_fused_tail_f16(h, one, one, one, two, one, f, 2, one, 1, None, None),
+        "moe_gemm_phase": lambda: lib.ferrum_hip_moe_gemm_phase_f16(h, one, one, one, one, one, 8, 16, 2, 4, 0, None),
+        "moe_gemm_phase_inline_align": lambda: lib.ferrum_hip_moe_gemm_phase_inline_align_f16(h, one, one, one, 8, 4, 2, 4, 0, None),
+        "moe_gemm_phase_expert_major": lambda: lib.ferrum_hip_moe_gemm_phase_expert_major_f16(h, one, one, one, 8, 4, 2, 0, None),
+        "moe_gemm_phase_expert_major_pair": lambda: lib.ferrum_hip_moe_gemm_phase_expert_major_pair_f16(h, h2, one, one, one, one, 8, 4, 2, None),
+        "merge_route": lambda: lib.ferrum_hip_moe_gemm_phase_merge_route_f16(h, one, one, one, one, 4, 2, 2, 1, 32, 4, 0, one, one, one, one, one, None),
+        "gemm_phase_batched": lambda: lib.ferrum_hip_moe_gemm_phase_batched_f16(h, one, one, 1, one, 2048, 0, None),
+    }
+    for name, call in calls.items():
+        assert call() == 2, name
+        err = lib.ferrum_hip_last_error()
+        assert name.encode() in err and b"carries no weights" in err, (name, err)
+    assert lib.ferrum_hip_gptq_linear_can_fuse_tail(h, 1) == 0
+    k, n, e = C.c_int(), C.c_int(), C.c_int()
+    assert lib.ferrum_hip_gptq_info(h, C.byref(k), C.byref(n), C.byref(e), None) == 0 and (k.value, n.value, e.value) == (2048, 512, 0)

@@ -475,3 +475,166 @@ def test_fused_tail_bounds_pass_float32_emulation_and_flag_faults(oracle, k, sym
     _flagged(lambda: pb.assert_within(ref, tol, gemm(total - ssv[:, -1]), "last vector left out of the row sum"))
     _flagged(lambda: pb.assert_within(ref, tol, gemm(np.roll(total, 1)), "the previous row's sum of squares"))
     _flagged(lambda: pb.assert_within(ref, tol, gemm(rows=r_in), "GEMM on residual_in"))
+
+
+# ── decode attention of the chain: bound, restatement, planted contexts, injected faults ─────────────────────────────────
+def _attn_case(kv_len, window, splits, G, seed=0, spare=3):
+    rng = np.random.default_rng(seed * 100003 + kv_len * 31 + window * 7 + splits)
+    q = pb.f16r(1.5 * rng.standard_normal((G, 128)))
+    k_new, v_new = pb.f16r(rng.standard_normal(128)), pb.f16r(rng.standard_normal(128))
+    ctx = pb.plant_context(rng, q, k_new, kv_len, window, splits, pb._cdiv(kv_len, 16) + spare)
+    K, V = pb.effective_kv(ctx, k_new, v_new, kv_len)
+    ref, tol, w = pb.decode_attn_ref_tol(q, K, V, ctx["allowed"], kv_len, window, splits)
+    return dict(q=q, k_new=k_new, v_new=v_new, ctx=ctx, K=K, V=V, ref=ref, tol=tol, w=w, kv_len=kv_len, window=window, splits=splits)
+
+
+def _emulate_attn(c, fault=None, fault_range=0):
+    return pb.chain_attn_emulate(c["q"], c["ctx"]["K"], c["ctx"]["V"], c["k_new"], c["v_new"], c["kv_len"], c["window"], c["splits"],
+                                 fault=fault, fault_range=fault_range)
+
+
+def _attn_flagged(c, out):
+    with np.errstate(invalid="ignore"):
+        return bool((~(np.abs(out.astype(np.float64) - c["ref"]) <= c["tol"])).any())
+
+
+@pytest.mark.parametrize("name", sorted(pb.ATTN_CASES))
+def test_attention_restatement_is_inside_the_bound_and_planted_keys_weigh_2_to_20_percent(name):
+    """At every context of the GPU module's cases: the float32 / fp16 restatement of chain_role_attn lies inside the bound; on
+    the float64 reference alone every planted key carries 2–20 % of the mass of the row it was planted for, and every poisoned
+    position would carry more than 50 % of every row if it were counted."""
+    nkv, splits, window, contexts = pb.ATTN_CASES[name]
+    G = 32 // nkv
+    worst, planted = 0.0, 0
+    for kv_len in contexts:
+        c = _attn_case(kv_len, window, splits, G)
+        ctx = c["ctx"]
+        for p, h in zip(ctx["edges"], ctx["heads"]):
+            assert pb.PLANT_MASS[0] <= c["w"][h, p] <= pb.PLANT_MASS[1], (name, kv_len, p, h, c["w"][h, p])
+            planted += 1
+        assert not set(ctx["edges"]) & set(ctx["poison"]) and not c["w"][:, [p for p in ctx["poison"] if p != kv_len - 1]].any()
+        s_all = pb.ATTN_SCALE * (c["q"].astype(np.float64) @ c["K"][ctx["allowed"]].T)
+        logZ = np.logaddexp.reduce(s_all, axis=1)
+        for p in ctx["poison"]:
+            s_p = pb.ATTN_SCALE * (c["q"].astype(np.float64) @ ctx["K"][p])
+            assert np.all(s_p > logZ), (name, kv_len, p)                    # e^s_p / (Z + e^s_p) > 1/2 on every row
+            assert np.all(np.abs(ctx["V"][p]) == pb.POISON_V)
+        out = _emulate_attn(c)
+        ratio = float((np.abs(out.astype(np.float64) - c["ref"]) / c["tol"]).max())
+        assert ratio < 1.0, (name, kv_len, ratio)
+        worst = max(worst, ratio)
+    assert planted or window == 1                             # (a window of one key holds the new token alone: nothing to plant)
+    print(f"attention restatement {name}: largest err/tol {worst:.3f}")
+
+
+ATTN_FAULT_CASES = [
+    # (fault, kv_len, window, splits, G, ranges the fault is applied to)
+    ("drop_last_key_of_range", 300, 0, 5, 8, (0, 1, 2, 3)),
+    ("drop_last_key_of_range", 2064, 0, 5, 8, (0, 3)),
+    ("drop_last_key_of_range", 257, 150, 16, 2, (2, 5)),           # six pairs over 16 ranges: ranges 2, 5, 7, 10, 13, 15 hold one each
+    ("first_key_of_next_range_twice", 300, 0, 5, 8, (0, 1, 2, 3)),
+    ("first_key_of_next_range_twice", 2064, 0, 16, 4, (0, 14)),
+    ("win_lo_one_low", 257, 150, 1, 8, (0,)),
+    ("win_lo_one_low", 18, 17, 1, 8, (0,)),
+    ("win_lo_one_low", 2, 1, 1, 8, (0,)),
+    ("win_lo_one_low", 300, 150, 5, 4, (0,)),
+    ("win_lo_one_high", 257, 150, 1, 8, (0,)),
+    ("win_lo_one_high", 17, 16, 5, 8, (0,)),
+    ("win_lo_one_high", 300, 150, 16, 2, (0,)),
+    ("slot_past_kv_len", 250, 0, 1, 8, (0,)),
+    ("slot_past_kv_len", 17, 0, 5, 4, (0,)),
+    ("slot_past_kv_len", 1, 0, 1, 8, (0,)),
+    ("slot_past_kv_len", 2064, 0, 5, 8, (0,)),
+    ("absent_second_block", 33, 0, 1, 8, (0,)),
+    ("absent_second_block", 257, 0, 5, 8, (0,)),
+    ("absent_second_block", 2064, 0, 1, 2, (0,)),
+    ("absent_second_block", 1, 0, 1, 8, (0,)),
+    ("new_token_from_pool", 1, 0, 1, 8, (0,)),
+    ("new_token_from_pool", 16, 0, 1, 8, (0,)),
+    ("new_token_from_pool", 300, 0, 5, 4, (0,)),
+    ("new_token_from_pool", 1040, 0, 1, 8, (0,)),
+    ("range_left_out", 300, 0, 5, 8, (0, 1, 2, 3, 4)),
+    ("range_left_out", 2064, 0, 16, 2, (0, 9, 15)),
+    ("range_left_out", 33, 0, 5, 8, (4,)),                    # two pairs over five ranges: only ranges 2 and 4 hold one
+    ("stale_m", 300, 0, 5, 8, (1, 2, 3, 4)),
+    ("stale_m", 2064, 0, 5, 4, (1, 4)),
+    ("neighbour_q", 300, 0, 1, 8, (0,)),
+    ("neighbour_q", 16, 0, 5, 4, (0,)),
+    ("neighbour_q", 129, 0, 16, 2, (0,)),
+    ("window_not_reloaded", 1040, 0, 1, 8, (0,)),
+    ("window_not_reloaded", 2064, 0, 1, 8, (0,)),
+]
+
+
+@pytest.mark.parametrize("fault,kv_len,window,splits,G,ranges", ATTN_FAULT_CASES, ids=[f"{c[0]}-{c[1]}-w{c[2]}-s{c[3]}-g{c[4]}" for c in ATTN_FAULT_CASES])
+def test_attention_bound_flags_every_injected_fault(fault, kv_len, window, splits, G, ranges):
+    """Each fault, applied to the clean restatement with the footprint the kernel would give it, leaves an element of the
+    affected rows (the G rows of the kv head) outside the bound.  No fault may go unflagged."""
+    c = _attn_case(kv_len, window, splits, G, seed=1)
+    assert not _attn_flagged(c, _emulate_attn(c))
+    for r in ranges:
+        assert _attn_flagged(c, _emulate_attn(c, fault, r)), (fault, kv_len, window, splits, G, r)
+
+
+def test_every_attention_fault_has_a_case():
+    assert {c[0] for c in ATTN_FAULT_CASES} == set(pb.ATTN_FAULTS)
+
+
+# ── routing without logits ───────────────────────────────────────────────────────────────────────────────────────────────
+def _routing(E=60, Q=4, K=4, T=6, H=256, seed=3):
+    rng = np.random.default_rng(seed)
+    x, w = pb.f16r(rng.standard_normal((T, H))), pb.f16r(rng.standard_normal((E, H)) / np.sqrt(H))
+    w[17], w[33] = w[2], w[2]                                                  # a tied group across parts
+    L, tol = pb.route_logits_ref_tol(x, w)
+    l32 = (x.astype(np.float32) @ w.astype(np.float32).T)
+    l32[:, 17], l32[:, 33] = l32[:, 2], l32[:, 2]
+    order = np.lexsort((np.arange(E)[None, :].repeat(T, 0), -l32), axis=1)
+    ids = order[:, :K]
+    p = np.exp(l32.astype(np.float64) - l32.max(axis=1, keepdims=True))
+    p /= p.sum(axis=1, keepdims=True)
+    wts = np.take_along_axis(p, ids, 1)
+    EQ = pb._cdiv(E, 16) // Q * 16
+    cl, ci, st = np.full((T, Q, 8), -np.inf, np.float32), np.full((T, Q, 8), 0x7fffffff, np.int64), np.zeros((T, Q, 2), np.float32)
+    for t in range(T):
+        for q in range(Q):
+            own = np.arange(q * EQ, min(E, (q + 1) * EQ))
+            o = own[np.lexsort((own, -l32[t, own]))][:K]
+            ci[t, q, :len(o)], cl[t, q, :len(o)] = o, l32[t, o]
+            st[t, q] = l32[t, own].max(), np.exp(l32[t, own] - l32[t, own].max()).sum()
+    return dict(L=L, tol=tol, ids=ids, wts=wts / wts.sum(axis=1, keepdims=True), cl=cl, ci=ci, st=st, Q=Q, K=K, l32=l32)
+
+
+def test_routing_checks_pass_a_clean_router_and_flag_its_faults():
+    r = _routing()
+    pb.assert_route_selection(r["L"], r["tol"], r["ids"], r["wts"], True)
+    pb.assert_route_ties(r["ids"], [[2, 17, 33]])
+    pb.assert_route_lists(r["L"], r["tol"], r["cl"], r["ci"], r["st"], r["Q"], r["K"])
+    T, E = r["L"].shape
+    worst = np.argsort(r["l32"][0])[0]
+
+    def bad(fn, **kw):
+        with pytest.raises(AssertionError):
+            fn(**kw)
+    ids = r["ids"].copy(); ids[0, -1] = worst                                  # a far-worse expert chosen
+    bad(lambda: pb.assert_route_selection(r["L"], r["tol"], ids, r["wts"], True))
+    ids = r["ids"].copy(); ids[0, [0, -1]] = ids[0, [-1, 0]]                   # ranks swapped
+    bad(lambda: pb.assert_route_selection(r["L"], r["tol"], ids, r["wts"][:, ::-1] if False else r["wts"], True))
+    w = r["wts"].copy(); w[1, 0] *= 1.001                                      # one combine weight off by 0.1 %
+    bad(lambda: pb.assert_route_selection(r["L"], r["tol"], r["ids"], w, True))
+    bad(lambda: pb.assert_route_selection(r["L"], r["tol"], r["ids"], r["wts"], False))      # renormalised where it should not be
+    bad(lambda: pb.assert_route_ties(np.array([[17, 2, 5, 6]]), [[2, 17, 33]]))             # higher id first
+    bad(lambda: pb.assert_route_ties(np.array([[2, 33, 5, 6]]), [[2, 17, 33]]))             # a lower id skipped
+    assert pb.assert_route_ties(np.array([[5, 2, 17, 6]]), [[2, 17, 33]]) == 1              # the boundary cuts the group: counted
+    for name, mutate in {
+        "order": lambda cl, ci, st: (cl.__setitem__((0, 0, [0, 1]), cl[0, 0, [1, 0]]), ci.__setitem__((0, 0, [0, 1]), ci[0, 0, [1, 0]])),
+        "value": lambda cl, ci, st: cl.__setitem__((0, 1, 2), cl[0, 1, 2] * np.float32(1.01)),
+        "coverage": lambda cl, ci, st: (ci.__setitem__((0, 0, 3), np.argsort(r["l32"][0, :16])[0]), cl.__setitem__((0, 0, 3), np.sort(r["l32"][0, :16])[0])),
+        "unused": lambda cl, ci, st: ci.__setitem__((0, 0, 5), 3),
+        "max": lambda cl, ci, st: st.__setitem__((0, 2, 0), np.nextafter(st[0, 2, 0], np.float32(9))),
+        "sumexp": lambda cl, ci, st: st.__setitem__((0, 3, 1), st[0, 3, 1] * np.float32(1.001)),
+    }.items():
+        cl, ci, st = r["cl"].copy(), r["ci"].copy(), r["st"].copy()
+        mutate(cl, ci, st)
+        with pytest.raises(AssertionError):
+            pb.assert_route_lists(r["L"], r["tol"], cl, ci, st, r["Q"], r["K"])
+            pytest.fail(name)
