@@ -245,6 +245,18 @@ impl Default for EmbedOptions {
     }
 }
 
+/// One target's answer from `score_tokens` (`FerrumHipTokenScore`): `token == top_token` exactly when greedy decoding would
+/// have produced the token.
+#[derive(Clone, Copy, Debug, PartialEq)]
+pub struct TokenScore {
+    pub logprob: f32,
+    pub top_logprob: f32,
+    pub top_token: u32,
+}
+
+/// Sequence ids of `score_tokens`: beside the range of `embed_tokens`, as far from the cache-id map.
+const SCORE_SEQ_BASE: u64 = (1 << 63) + (1 << 62);
+
 /// Sequence ids of `embed_tokens`: a range the cache-id map (counting up from 1) never reaches; each call releases its own.
 const EMBED_SEQ_BASE: u64 = 1 << 63;
 
@@ -285,6 +297,34 @@ impl HipDecoderModel {
         }
         check(rc)?;
         Ok(out.chunks(d).map(|v| v.to_vec()).collect())
+    }
+
+    /// Log-probabilities of given tokens (`ferrum_hip_model_score`): one forward over the token sequences, each whole in the
+    /// call and released before it returns; `targets` are (sequence, row, token) — log p(token) under the distribution after
+    /// `seqs[sequence][row]` was consumed.  One `TokenScore` per target, in target order: what the `logprobs` fields of a
+    /// chat / completions response and an evaluation harness's loglikelihood are filled from.  The batch must fit the
+    /// runner's max_seqs / max_tokens; the caller splits larger requests.
+    pub fn score_tokens(&self, seqs: &[&[u32]], targets: &[(usize, usize, u32)]) -> Result<Vec<TokenScore>> {
+        let c_items: Vec<ffi::FerrumHipBatchItem> = seqs.iter().enumerate().map(|(j, toks)| ffi::FerrumHipBatchItem {
+            seq_id: SCORE_SEQ_BASE + j as u64, q_tokens: toks.as_ptr(), num_q_tokens: toks.len() as i32, pos_offset: 0, is_final_chunk: 1, _pad: 0,
+        }).collect();
+        let c_targets: Vec<ffi::FerrumHipScoreTarget> = targets.iter().map(|&(item, row, token)| ffi::FerrumHipScoreTarget {
+            item: item as i32, row: row as i32, token, _pad: 0,
+        }).collect();
+        let c_opts = ffi::FerrumHipScoreOptions { max_rows_per_pass: 0, release: 1 };
+        let mut out = vec![ffi::FerrumHipTokenScore { logprob: 0.0, top_logprob: 0.0, top_token: 0, _pad: 0 }; targets.len()];
+        let rc = unsafe {
+            ffi::ferrum_hip_model_score(self.m, c_items.as_ptr(), c_items.len() as c_int, c_targets.as_ptr(), c_targets.len() as c_int,
+                                        &c_opts, out.as_mut_ptr())
+        };
+        if rc != ffi::FERRUM_HIP_OK {
+            // (a forward that failed behind the admission has not released: nothing of this call may stay reserved)
+            for it in &c_items {
+                unsafe { ffi::ferrum_hip_model_release(self.m, it.seq_id) };
+            }
+        }
+        check(rc)?;
+        Ok(out.iter().map(|s| TokenScore { logprob: s.logprob, top_logprob: s.top_logprob, top_token: s.top_token }).collect())
     }
 
     fn blocks_of(&self, id: u64) -> usize {

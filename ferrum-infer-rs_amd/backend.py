@@ -259,6 +259,19 @@ class HipBackend:
                   int(num_seqs), int(dim), ctx.ws, ctx.stream), "embed_pool")
 
     @staticmethod
+    def logprob_rows(ctx, logits, pair_rows, pair_tokens, pair_logprob, row_lse=None, row_top=None, m=None, n=None, ld=None):
+        """The scoring head (csrc/score_head.hip): logits [m, n] fp32 with row stride ld (default: the tensor's own shape and
+        n); per row the log-sum-exp into row_lse [m] fp32 and the first maximum into row_top [m] (uint32 bit patterns in an int32
+        tensor), either may be None; per pair (pair_rows int32, pair_tokens int32 holding uint32) the log-prob into pair_logprob
+        fp32."""
+        m = logits.shape[0] if m is None else m
+        n = logits.shape[-1] if n is None else n
+        ld = n if ld is None else ld
+        num_pairs = 0 if pair_rows is None else pair_rows.numel()
+        _check(ctx.lib.ferrum_hip_logprob_rows_f32(_ptr(logits), int(ld), int(m), int(n), _ptr(pair_rows), _ptr(pair_tokens), int(num_pairs),
+                                                   _ptr(pair_logprob), _ptr(row_lse), _ptr(row_top), ctx.ws, ctx.stream), "logprob_rows")
+
+    @staticmethod
     def layer_norm(ctx, x, gamma, beta, eps, out, tokens, dim):
         _check(ctx.lib.ferrum_hip_layer_norm_f16(_ptr(x), _ptr(gamma), _ptr(beta), C.c_float(eps), _ptr(out), tokens, dim, ctx.stream), "layer_norm")
 

@@ -179,6 +179,15 @@ int ferrum_hip_gather_columns_f16(const void* in, const int32_t* perm, void* out
     return gather_columns_f16(CH(in), perm, H(out), rows, cols, ST(stream));
 }
 
+// ── the scoring head (score_head.hip) ──
+int ferrum_hip_logprob_rows_f32(const float* logits, int ld, int m, int n, const int32_t* pair_rows, const uint32_t* pair_tokens,
+                                int num_pairs, float* pair_logprob, float* row_lse, uint32_t* row_top, FerrumHipWorkspace* ws, void* stream) {
+    FH_REQUIRE(m <= 0 || logits, "logprob_rows: null logits");
+    FH_REQUIRE(num_pairs <= 0 || (pair_rows && pair_tokens && pair_logprob), "logprob_rows: null pair buffer");
+    return logprob_rows_f32(logits, ld, m, n, pair_rows, pair_tokens, num_pairs, pair_logprob, row_lse, row_top, nullptr, ws ? ws->ptr : nullptr,
+                            ws ? ws->bytes : 0, ST(stream));
+}
+
 // ── the embedding tail (embed_pool.hip), exported for the element-wise tests ──
 static int embed_pool_export(const void* hidden, bool f32, const int32_t* seq_rows, const void* norm_w, float eps, int pooling, int normalize,
                              int dims, float* out, int num_seqs, int dim, FerrumHipWorkspace* ws, void* stream) {

@@ -140,6 +140,15 @@ int rms_norm_f32_to_f16(const float* x, const int32_t* row_idx, const __half* w,
 // length, fixed summation order).
 int embed_pool(const void* hidden, bool hidden_f32, const int32_t* seq_rows, const __half* norm_w, float eps, int pooling, int normalize,
                int dims, float* out, int num_seqs, int dim, int max_span_rows, float* workspace, size_t workspace_bytes, hipStream_t s);
+// ── scoring head (score_head.hip; launch plan: score_plan.h) ─────────────────
+// For every row r of logits [m, n] fp32 (row stride ld ≥ n): lse = log Σ exp x (fp32, maximum subtracted), top = the first maximum,
+// top log-prob = x[top] − lse; for every pair p: pair_logprob[p] = x[pair_rows[p]][pair_tokens[p]] − lse (−inf for a token ≥ n).
+// row_lse / row_top / row_top_logprob may be NULL.  Partials [m][⌈n / 4096⌉] × (max, sum, index) + [m] lse in the workspace, which
+// need not be zero; too small a workspace is refused (2), never worked around.  Bit-identical from run to run and whatever else
+// the launch holds (no atomics, seams at multiples of 4096, fixed summation order).  Only launches: capturable.
+int logprob_rows_f32(const float* logits, int ld, int m, int n, const int32_t* pair_rows, const uint32_t* pair_tokens, int num_pairs,
+                     float* pair_logprob, float* row_lse, uint32_t* row_top, float* row_top_logprob, float* workspace,
+                     size_t workspace_bytes, hipStream_t s);
 // contiguous-KV lane (contig_ops.hip)
 int split_qkv_f16(const __half* qkv, __half* q, __half* k, __half* v, int tokens, int q_dim, int kv_dim, hipStream_t s);
 int qk_norm_rope_f16(const __half* input, const __half* norm_w, const float* cos_t, const float* sin_t, __half* output,

@@ -121,6 +121,13 @@ struct FerrumHipModel {
     uint32_t* out_tokens = nullptr;   // [max_seqs]
     float* embed_out = nullptr;       // [max_seqs, hidden] fp32: the vectors of ferrum_hip_model_embed (allocated by its first call)
     size_t embed_out_bytes = 0;
+    // ferrum_hip_model_score, allocated by its first call and only ever grown (score_plan.h sizes them): one pass's normed rows
+    // [C, hidden] fp16 and logits [C, V] fp32, the row / pair lists, the results
+    __half* score_hidden = nullptr;
+    float* score_logits = nullptr;
+    int32_t* score_lists = nullptr;
+    float* score_results = nullptr;
+    size_t score_hidden_bytes = 0, score_logits_bytes = 0, score_lists_bytes = 0, score_results_bytes = 0;
     float* workspace = nullptr;
     size_t workspace_bytes = 0;
     float* taps = nullptr;         // [L, max_tokens, H] fp32 when enabled
@@ -208,9 +215,23 @@ struct GreedyDeviceOpts {          // device pointers, already uploaded on m->st
 // stream into out [num_sampled, dims ? dims : hidden] fp32 (embed_pool.hip)
 struct EmbedHead { int pooling, normalize, dims; bool final_norm; int max_span_rows; float* out; };
 
+// The scoring head in place of the sampling head (score_head.hip): per pass of the plan (score_plan.h; the begins are host
+// arrays of num_passes + 1 entries), the listed rows of the residual stream through the final norm and the lm_head, then the
+// log-sum-exp, first maximum and the pairs' log-probs.  Everything else is a device pointer: rows [R], pair_rows / pair_tokens /
+// pair_logprob [T], row_top_logprob / row_top [R].
+struct ScoreHead {
+    int num_passes;
+    const int32_t *pass_row_begin, *pass_pair_begin;
+    const int32_t *rows, *pair_rows;
+    const uint32_t* pair_tokens;
+    float *pair_logprob, *row_top_logprob;
+    uint32_t* row_top;
+};
+
 // runner_forward.hip
 int enqueue_forward(FerrumHipModel* m, const StepShape& sh, bool greedy, const GreedyDeviceOpts* gopts = nullptr,
-                    const DecodeAdvance* advance = nullptr, int* advance_fused = nullptr, const EmbedHead* embed = nullptr);
+                    const DecodeAdvance* advance = nullptr, int* advance_fused = nullptr, const EmbedHead* embed = nullptr,
+                    const ScoreHead* score = nullptr);
 const int32_t* moe_ids(const FerrumHipModel* m);
 int moe_max_blocks(int P, int E);
 bool moe_expert_major(const FerrumHipModel* m, int P);

@@ -702,6 +702,20 @@ struct ForwardPass {
         return embed_pool(rows, sandwich, ix.embed_spans, eh.final_norm ? m->final_norm : nullptr, c.rms_eps, eh.pooling, eh.normalize, eh.dims,
                           eh.out, sh.num_sampled, H, eh.max_span_rows, m->workspace, m->workspace_bytes, s);
     }
+    // the scoring head instead: the rows the targets name, a pass at a time, through what sample_head runs on its rows (final
+    // norm, lm_head) and then the log-sum-exp / first maximum / gather of score_head.hip on the pass's logits
+    int score_head(const ScoreHead& h) {
+        for (int q = 0; q < h.num_passes; q++) {
+            const int r0 = h.pass_row_begin[q], n = h.pass_row_begin[q + 1] - r0;
+            const int p0 = h.pass_pair_begin[q], pairs = h.pass_pair_begin[q + 1] - p0;
+            if (sandwich) RUN(rms_norm_f32_to_f16(m->residual_f32, h.rows + r0, m->final_norm, c.rms_eps, m->score_hidden, n, H, s));
+            else RUN(gather_rms_norm_f16(m->residual, h.rows + r0, m->final_norm, c.rms_eps, m->score_hidden, n, H, s));
+            RUN(f16t_gemm_f32out(m->score_hidden, m->lm_head_t, m->score_logits, n, c.vocab, H, m->workspace, m->workspace_bytes, s));
+            RUN(logprob_rows_f32(m->score_logits, c.vocab, n, c.vocab, h.pair_rows + p0, h.pair_tokens + p0, pairs, h.pair_logprob + p0, nullptr,
+                                 h.row_top + r0, h.row_top_logprob + r0, m->workspace, m->workspace_bytes, s));
+        }
+        return 0;
+    }
 };
 #undef RUN
 
@@ -709,9 +723,9 @@ struct ForwardPass {
 
 // Enqueue one forward: head, the layers — each as one of the chain forms (decided per layer, the next layer's decision known, so
 // that a tail can be left to its launch) or as q|k|v + attention and the MLP block — then the sampling head, or (`embed`) the
-// embedding tail in its place.
+// embedding tail, or (`score`) the scoring head in its place.
 int fh::enqueue_forward(FerrumHipModel* m, const StepShape& sh, bool greedy, const GreedyDeviceOpts* gopts, const DecodeAdvance* advance,
-                        int* advance_fused, const EmbedHead* embed) {
+                        int* advance_fused, const EmbedHead* embed, const ScoreHead* score) {
     if (advance_fused) *advance_fused = 0;
     const int n_layers = m->cfg.num_layers;
     ForwardPass f(m, sh);
@@ -734,6 +748,7 @@ int fh::enqueue_forward(FerrumHipModel* m, const StepShape& sh, bool greedy, con
     }
     m->taps_tokens = sh.m_total;
     if (embed) return f.embed_head(*embed);
+    if (score) return f.score_head(*score);
     return f.sample_head(greedy, gopts, advance, advance_fused);
 }
 #undef FH_TRY

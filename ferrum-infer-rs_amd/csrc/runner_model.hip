@@ -191,7 +191,8 @@ int ferrum_hip_model_destroy(FerrumHipModel* m) {
                     (void*)m->route_cand, (void*)m->route_stats, (void*)m->route_arrive, (void*)m->cos_local,
                     (void*)m->sin_local, (void*)m->residual_f32, (void*)m->gather_scratch, (void*)m->greedy_opts_dev, (void*)m->tp_tmp,
                     (void*)m->expert_ids_local, (void*)m->ones, m->vp_pairs, m->vp_gathered,
-                    (void*)m->kv_pools_dev, (void*)m->kv_pairs_dev, (void*)m->kv_staging, (void*)m->embed_out})
+                    (void*)m->kv_pools_dev, (void*)m->kv_pairs_dev, (void*)m->kv_staging, (void*)m->embed_out,
+                    (void*)m->score_hidden, (void*)m->score_logits, (void*)m->score_lists, (void*)m->score_results})
         if (p) (void)hipFree(p);
     if (m->idx_host) (void)hipHostFree(m->idx_host);
     if (m->inlaunch_timeouts) (void)hipHostFree(m->inlaunch_timeouts);

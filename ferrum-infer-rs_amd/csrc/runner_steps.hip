@@ -1,9 +1,11 @@
 // Decoder runner, the drivers of the forward: ferrum_hip_model_unified_forward{,_ex} (admission, index block, one forward),
-// ferrum_hip_model_embed (the same forward with the embedding tail in place of the sampling head),
+// ferrum_hip_model_embed (the same forward with the embedding tail in place of the sampling head), ferrum_hip_model_score (… with
+// the scoring head in its place),
 // ferrum_hip_model_decode_steps (the steady-state decode loop: one step captured into a hipGraph and replayed) and the bench's
 // ferrum_hip_model_time_kernel.
 #include "runner.h"
 #include "knobs.h"
+#include "score_plan.h"
 #include "tp_comm.h"
 
 using namespace fh;
@@ -222,6 +224,69 @@ int ferrum_hip_model_embed(FerrumHipModel* m, const FerrumHipBatchItem* items, i
     if (o.release)
         for (int i = 0; i < num_items; i++)
             if (items[i].is_final_chunk) (void)ferrum_hip_model_release(m, items[i].seq_id);
+    return rc;
+}
+
+int ferrum_hip_model_score(FerrumHipModel* m, const FerrumHipBatchItem* items, int num_items, const FerrumHipScoreTarget* targets,
+                           int num_targets, const FerrumHipScoreOptions* opts, FerrumHipTokenScore* out_host) {
+    FH_REQUIRE(m && m->finalized, "model_score: model not finalized");
+    const FerrumHipModelConfig& c = m->cfg;
+    if (c.vocab_parallel) {
+        fh::set_error("model_score: a vocabulary-parallel lm_head is not scored (the log-sum-exp of a sharded row needs a merge across ranks)");
+        return 3;
+    }
+    const FerrumHipScoreOptions o = opts ? *opts : FerrumHipScoreOptions{0, 0};
+    // pre-flight: nothing is reserved or launched for a request that cannot be served
+    FH_REQUIRE(num_items <= 0 || items, "model_score: null items");
+    FH_REQUIRE(num_targets <= 0 || targets, "model_score: null targets");
+    FH_REQUIRE(num_targets <= 0 || out_host, "model_score: null output with %d targets", num_targets);
+    std::vector<int32_t> item_rows(std::max(num_items, 0));
+    for (int i = 0; i < num_items; i++) item_rows[i] = items[i].num_q_tokens;
+    std::vector<ScoreTargetRef> refs(std::max(num_targets, 0));
+    for (int t = 0; t < num_targets; t++) refs[t] = {targets[t].item, targets[t].row, targets[t].token};
+    ScoreBatchPlan plan;
+    char why[256];
+    if (score_batch_plan(ScoreBatchShape{num_items, item_rows.data(), num_targets, refs.data(), c.vocab, c.hidden, c.max_tokens, o.max_rows_per_pass},
+                         &plan, why, sizeof(why))) {
+        fh::set_error("%s", why);
+        return 2;
+    }
+    FH_REQUIRE(plan.workspace_bytes <= m->workspace_bytes, "model_score: a pass of %d rows needs a workspace of %zu bytes, the model has %zu",
+               plan.pass_rows, plan.workspace_bytes, m->workspace_bytes);
+    if (num_items == 0) return 0;
+    const int T = num_targets, R = plan.num_rows;
+    if (T > 0) {
+        if (int rc = grow_device((void**)&m->score_hidden, &m->score_hidden_bytes, plan.hidden_bytes, m->stream)) return rc;
+        if (int rc = grow_device((void**)&m->score_logits, &m->score_logits_bytes, plan.logits_bytes, m->stream)) return rc;
+        if (int rc = grow_device((void**)&m->score_lists, &m->score_lists_bytes, plan.lists_bytes, m->stream)) return rc;
+        if (int rc = grow_device((void**)&m->score_results, &m->score_results_bytes, plan.results_bytes, m->stream)) return rc;
+    }
+    StepShape sh{};
+    if (int rc = admit_and_upload(m, items, num_items, "model_score", &sh)) return rc;
+    std::vector<float> results((size_t)T + 2 * (size_t)R);      // pair log-probs [T] | row top log-probs [R] | row top tokens [R]
+    ScoreHead head{};
+    if (T > 0) {
+        int32_t* lists = m->score_lists;                         // rows [R] | pair_rows [T] | pair_tokens [T]
+        FH_CHECK_HIP(hipMemcpyAsync(lists, plan.rows.data(), (size_t)R * 4, hipMemcpyHostToDevice, m->stream));
+        FH_CHECK_HIP(hipMemcpyAsync(lists + R, plan.pair_rows.data(), (size_t)T * 4, hipMemcpyHostToDevice, m->stream));
+        FH_CHECK_HIP(hipMemcpyAsync(lists + R + T, plan.pair_tokens.data(), (size_t)T * 4, hipMemcpyHostToDevice, m->stream));
+        head = ScoreHead{plan.num_passes, plan.pass_row_begin.data(), plan.pass_pair_begin.data(), lists, lists + R,
+                         reinterpret_cast<const uint32_t*>(lists + R + T), m->score_results, m->score_results + T,
+                         reinterpret_cast<uint32_t*>(m->score_results + T + R)};
+    }
+    if (int rc = enqueue_forward(m, sh, false, nullptr, nullptr, nullptr, nullptr, &head)) return rc;
+    if (T > 0) FH_CHECK_HIP(hipMemcpyAsync(results.data(), m->score_results, results.size() * 4, hipMemcpyDeviceToHost, m->stream));
+    FH_CHECK_HIP(hipStreamSynchronize(m->stream));
+    for (int i = 0; i < num_items; i++) m->seqs->advance(items[i].seq_id, items[i].num_q_tokens);
+    const int rc = check_inlaunch_waits(m);
+    for (int t = 0; t < T; t++) {
+        const int r = plan.target_pass[t] * plan.pass_rows + plan.target_pass_row[t];
+        uint32_t top;
+        memcpy(&top, &results[(size_t)T + R + r], 4);
+        out_host[t] = FerrumHipTokenScore{results[plan.target_pair[t]], results[(size_t)T + r], top, 0};
+    }
+    if (o.release)
+        for (int i = 0; i < num_items; i++) (void)ferrum_hip_model_release(m, items[i].seq_id);
     return rc;
 }
 

@@ -46,6 +46,21 @@ class EmbedOptions(C.Structure):
 POOLING = {"last": 0, "mean": 1, "first": 2}
 
 
+class ScoreTarget(C.Structure):
+    """FerrumHipScoreTarget: log p(token) under the distribution after q_tokens[row] of items[item]."""
+    _fields_ = [("item", C.c_int32), ("row", C.c_int32), ("token", C.c_uint32), ("_pad", C.c_uint32)]
+
+
+class TokenScore(C.Structure):
+    """FerrumHipTokenScore: one target's answer."""
+    _fields_ = [("logprob", C.c_float), ("top_logprob", C.c_float), ("top_token", C.c_uint32), ("_pad", C.c_uint32)]
+
+
+class ScoreOptions(C.Structure):
+    """FerrumHipScoreOptions."""
+    _fields_ = [("max_rows_per_pass", C.c_int32), ("release", C.c_int32)]
+
+
 class KvSlotRequest(C.Structure):
     _fields_ = [("seq_id", C.c_uint64), ("target_len", C.c_int32), ("_pad", C.c_int32)]
 
@@ -430,6 +445,40 @@ class HipModel:
         out = np.zeros((max(n_final, 1), d), np.float32)
         _check(self.lib.ferrum_hip_model_embed(self.h, arr, len(items), C.byref(opts), out.ctypes.data_as(C.POINTER(C.c_float))), "embed")
         return out[:n_final]
+
+    def score(self, items, targets, max_rows_per_pass=0, release=False):
+        """items as for unified_forward (is_final_chunk is not read); targets [(item, row, token)]: log p(token) under the
+        distribution after q_tokens[row] of items[item] (ferrum_hip_model_score).  Returns, in target order, a list of
+        (logprob, top_logprob, top_token).  Items without targets only fill the KV cache.  release: every item's sequence is
+        released before the call returns."""
+        keep = [np.ascontiguousarray(t, dtype=np.uint32) for _, t, _, _ in items]
+        arr = (BatchItem * max(len(items), 1))()
+        for i, (sid, _, pos, fin) in enumerate(items):
+            arr[i] = BatchItem(sid, keep[i].ctypes.data_as(C.POINTER(C.c_uint32)), len(keep[i]), pos, int(fin), 0)
+        tg = (ScoreTarget * max(len(targets), 1))()
+        for j, (item, row, token) in enumerate(targets):
+            tg[j] = ScoreTarget(int(item), int(row), int(token), 0)
+        out = (TokenScore * max(len(targets), 1))()
+        opts = ScoreOptions(int(max_rows_per_pass), int(bool(release)))
+        _check(self.lib.ferrum_hip_model_score(self.h, arr, len(items), tg, len(targets), C.byref(opts), out), "score")
+        return [(out[j].logprob, out[j].top_logprob, out[j].top_token) for j in range(len(targets))]
+
+    def loglikelihood(self, requests, seq_base=1 << 62, max_rows_per_pass=0):
+        """An evaluation harness's loglikelihood: requests [(context tokens, continuation tokens)] with at least one context token
+        and one continuation token each → [(sum of the continuation's log-probs, is_greedy)], is_greedy: every continuation token
+        is its row's first maximum.  One forward over one item (context + continuation)[:-1] per request, sequence ids seq_base +
+        index, released before the call returns; the batch must fit max_seqs / max_tokens."""
+        items, targets, spans = [], [], []
+        for j, (context, continuation) in enumerate(requests):
+            context, continuation = list(context), list(continuation)
+            if len(context) < 1 or len(continuation) < 1:
+                raise ValueError(f"loglikelihood: request {j} needs at least one context and one continuation token")
+            items.append((seq_base + j, (context + continuation)[:-1], 0, True))
+            spans.append((len(targets), len(targets) + len(continuation)))
+            targets += [(j, len(context) - 1 + k, tok) for k, tok in enumerate(continuation)]
+        scores = self.score(items, targets, max_rows_per_pass=max_rows_per_pass, release=True)
+        return [(float(sum(np.float64(s[0]) for s in scores[a:b])), all(s[2] == t[2] for s, t in zip(scores[a:b], targets[a:b])))
+                for a, b in spans]
 
     def embedding_dim(self):
         h = C.c_int()

@@ -121,6 +121,28 @@ int ferrum_hip_embed_pool_f16(const void* hidden, const int32_t* seq_rows, const
                               int dims, float* out, int num_seqs, int dim, FerrumHipWorkspace* ws, void* stream);
 int ferrum_hip_embed_pool_f32(const float* hidden, const int32_t* seq_rows, const void* norm_w, float eps, int pooling, int normalize,
                               int dims, float* out, int num_seqs, int dim, FerrumHipWorkspace* ws, void* stream);
+/* The scoring head (csrc/score_head.hip), device pointers: log-probabilities of given tokens from rows of logits — the OpenAI
+ * `logprobs` fields (ferrum-server/src/openai.rs) and an evaluation harness's loglikelihood are built on it.
+ * logits [m rows, n] fp32, row stride ld (>= n, elements).  For every row r: M = max, S = sum_i exp(x_i - M) in fp32,
+ * lse = M + log S, top = index of the FIRST maximum.  For every pair p: logprob[p] = x[pair_rows[p]][pair_tokens[p]] - lse.
+ *   - -inf entries contribute 0;
+ *   - a row with no entry above -inf has lse = -inf, top = 0, and every log-prob of that row is NaN (there is no distribution);
+ *   - a row holding a NaN has lse and all its log-probs NaN (the NaN travels through the sum; a maximum taken by comparison
+ *     would have dropped it); top is then unspecified;
+ *   - pair_tokens[p] >= n writes -INFINITY;
+ *   - pairs may come in any order, several may name one row, rows may have none;
+ *   - pair_rows outside [0, m) is the caller's error (ferrum_hip_model_score checks it on the host).
+ * m <= 65535.  A row is cut into segments of 4096 columns, one workgroup each, whose (max, sum, first argument) partials go to
+ * the workspace and are merged per row in segment order; a last launch gathers the pairs.  The workspace must hold
+ * (3 * m * ceil(n / 4096) + m) * 4 bytes and need not be zero; a smaller one is FERRUM_HIP_INVALID with the bytes needed in the
+ * message.  No atomics, seams at multiples of 4096 whatever m, ld or the address, every sum in a fixed order: a row's lse, top
+ * and log-probs are bit-identical from run to run, whatever m is and whichever other rows the launch holds.  expf / logf, not
+ * the fast forms.  Launches only (no allocation, copy or synchronisation): capturable into a graph. */
+int ferrum_hip_logprob_rows_f32(const float* logits, int ld, int m, int n,
+                                const int32_t* pair_rows, const uint32_t* pair_tokens, int num_pairs,
+                                float* pair_logprob,                 /* [num_pairs] */
+                                float* row_lse, uint32_t* row_top,   /* [m] each, either may be NULL */
+                                FerrumHipWorkspace* ws, void* stream);
 /* Backend::layer_norm / Backend::gelu (traits.rs, required core ops; CPU cpu.rs:2081-2122 — exact-form GELU with the
  * reference's own erf polynomial, cpu.rs:2263-2273).  Not on the LLM decode path; present so that the binding returns
  * "unsupported" for no required method. */
@@ -786,6 +808,42 @@ typedef struct {
 int ferrum_hip_model_embed(FerrumHipModel* model, const FerrumHipBatchItem* items, int num_items,
                            const FerrumHipEmbedOptions* opts, float* out_host);
 int ferrum_hip_model_embedding_dim(const FerrumHipModel* model, int* hidden);
+/* Scoring: log-probabilities of given tokens (`logprobs` of the chat / completions requests, openai.rs; an evaluation
+ * harness's loglikelihood(context, continuation); perplexity; yes/no rerankers).  The forward of
+ * ferrum_hip_model_unified_forward - same admission, KV writes and layers - with a scoring head in place of the sampling head:
+ * the distinct rows the targets name, in packed-row order and at most max_rows_per_pass (0: min(max_tokens, 256)) at a time,
+ * go through the final norm and the lm_head, and ferrum_hip_logprob_rows_f32 above (with its special values and its determinism
+ * rule) reduces each pass on the device; out_host[t] answers targets[t], copied back once.  A target (item, row, token) asks
+ * for log p(token) under the distribution AFTER q_tokens[row] of that item was consumed; any number of targets may name one
+ * row, in any order.  is_final_chunk is not read: the targets say which rows are scored, items without targets only fill the KV
+ * cache, num_targets == 0 is a valid KV-fill call.  top_token is the row's first maximum, so token == top_token exactly when
+ * greedy decoding would have produced the token.
+ * FERRUM_HIP_INVALID, before anything is reserved or launched and with the offending target named: item / row out of range,
+ * token >= vocab, negative counts, null out_host with targets present, max_rows_per_pass < 0.  A vocabulary-parallel model is
+ * FERRUM_HIP_UNSUPPORTED (a sharded log-sum-exp needs a cross-rank merge).  Under plain tensor parallelism the call is
+ * rank-local like ferrum_hip_model_embed.  The pass buffers ([C, hidden] fp16, [C, vocab] fp32, lists, results) are allocated by
+ * the first scoring call, only ever grow, and are freed by ferrum_hip_model_destroy: max_rows_per_pass bounds them.
+ * release != 0: every item's sequence is released before the call returns; release == 0 leaves sequences that decode_steps or
+ * a further forward continue. */
+typedef struct {
+    int32_t item;      /* index into items[] */
+    int32_t row;       /* query row of that item, 0 <= row < num_q_tokens: the distribution AFTER q_tokens[row] was consumed */
+    uint32_t token;    /* the token whose log-probability under that distribution is wanted */
+    uint32_t _pad;
+} FerrumHipScoreTarget;
+typedef struct {
+    float logprob;      /* log p(token) */
+    float top_logprob;  /* log p(top_token) */
+    uint32_t top_token; /* first maximum of the row: token == top_token <=> greedy decoding would have produced it */
+    uint32_t _pad;
+} FerrumHipTokenScore;
+typedef struct {
+    int32_t max_rows_per_pass;  /* 0 = default; else the head scores at most this many distinct rows per lm_head pass */
+    int32_t release;            /* != 0: release every item's sequence before returning (as FerrumHipEmbedOptions.release) */
+} FerrumHipScoreOptions;
+int ferrum_hip_model_score(FerrumHipModel* model, const FerrumHipBatchItem* items, int num_items,
+                           const FerrumHipScoreTarget* targets, int num_targets,
+                           const FerrumHipScoreOptions* opts, FerrumHipTokenScore* out_host /* [num_targets], target order */);
 /* Steady-state decode: every listed sequence advances by one token (its last sampled token),
  * `steps` times, with device-side greedy sampling and hipGraph replay when available.
  * out_tokens [steps, n] (may be NULL). */
